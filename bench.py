@@ -10,6 +10,12 @@ head, hierarchical loss, full backward, (N>1: RCCL gradient all-reduce), SGD-mom
 and re-derivation of the 16-bit compute copies.  8 images x 64 objects per GPU -> 32 256 ordered pairs per GPU and
 step.  Weak scaling: every rank owns 8 images.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, W warm-up steps, K timed steps, the line (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step`` = wall time of the K timed steps / K).  ``--full`` adds everything else
+the benchmark measures: per-kernel HIP-event timers in the timed steps, the roofline / HBM records, one single-stream pass for the
+backward's kernel times, the box-size sensitivity sweep, the pass with every sharing identity off and the CPU-oracle baseline.
+``--dump-outputs DIR`` writes what the timed path handed its caller in the last timed step (``write_outputs``).
+
 Multi-GPU: one process per GPU.  Under ``python -m torch.distributed.run --nproc-per-node N bench.py --gpus N`` the ranks
 come from the environment (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*; the reference spawns them with ``mp.spawn``,
 ``main.py:103,112-123``).  Called directly with ``--gpus N`` (N > 1) this file is its own launcher: the parent starts N
@@ -52,6 +58,66 @@ PMC_TAGS = ("r06_final", "r05_final7", "r05_final6", "r05_final5", "r05_final3",
 
 
 BENCH_LR_SCALE = 1e-3
+# the fields of a plain run's line (without --full)
+PLAIN_FIELDS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                "data", "config", "loss", "loss_first_step", "host", "backward_streams", "image_group_lanes", "peak_memory_gb", "ranks_seen",
+                "rank_ms_per_step", "dp_mode", "exposed_comm_ms")
+DUMP_SAMPLE = 1 << 21          # --dump-outputs: larger tensors are written as this many elements at fixed seeded positions
+
+
+def usable_cpus():
+    """Host threads this process may really use: ``os.cpu_count()`` counts the whole machine, a job is often given fewer
+    (affinity mask, cgroup CPU quota, OMP_NUM_THREADS set by whoever started it)."""
+    n = os.cpu_count() or 8
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "") or n))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
+def write_outputs(out_dir, loss, outputs, model):
+    """``--dump-outputs``: what a caller of the timed path holds after its last timed step, one ``<name>.npy`` per array - ``loss``
+    (float64 [1]), the step's pair outputs ``out_<field>`` (``PairOutputs``: relation log-probs, super-relation, connectivity, fc2
+    hidden, candidate scores / predicates) and, unless ``--forward-only``, every parameter after the update (``param_<name>``), all
+    float32, in their own shapes.  A tensor of more than DUMP_SAMPLE elements is written as DUMP_SAMPLE elements of its flattened form
+    at sorted positions drawn from a generator seeded by its name, the same in every run: two builds compare output for output
+    (about 45 MB in all at the default workload)."""
+    import zlib
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = []
+    if loss is not None:
+        arrays.append(("loss", torch.tensor([float(loss)], dtype=torch.float64)))
+    if outputs is not None:
+        for f in ("relation", "super_relation", "connectivity", "hidden", "cand_conf", "cand_pred"):
+            t = getattr(outputs, f, None)
+            if t is not None:
+                arrays.append(("out_" + f, t))
+    if model is not None:
+        arrays += [("param_" + n, p) for n, p in model.named_parameters()]
+    total = 0
+    for name, t in arrays:
+        t = t.detach()
+        if t.numel() > DUMP_SAMPLE:
+            t = t.flatten()
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(t.numel(), DUMP_SAMPLE, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    assert total <= 64 << 20, "dumped outputs exceed 64 MB: %d bytes" % total
 
 
 def parse_args(argv=None):
@@ -78,6 +144,12 @@ def parse_args(argv=None):
     ap.add_argument("--box-dist", default="survey", choices=["survey", "vg03", "vg06", "vg12"],
                     help="survey: SURVEY 8d's boxes (the benchmark); vgNN: raw boxes with ASSUMED VG-like marginals (median area NN %% of the "
                          "image) through the reference's own box pipeline (synthetic.vg_like_boxes, tools/vg_box_statistic.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel timers, roofline / HBM records, single-stream pass, box-size sensitivity, identity-off pass "
+                         "and CPU baseline (a plain run: set-up, warm-up, timed steps, the headline line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps: the last timed step's loss, pair outputs and updated parameters as DIR/<name>.npy "
+                         "(float32 / float64; tensors above 2^21 elements as a fixed seeded sample)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / rendezvous / reduction plumbing only, no GPU work (the CPU test of the N-rank launch uses it with gloo)")
     return ap.parse_args(argv)
@@ -271,7 +343,7 @@ def cpu_baseline(cfg, sd, reps=5, steps_per_rep=16, threads=None):
     from oracle import relhead_oracle as O
     from scene_graph_commonsense_amd.synthetic import make_scene_batch, predicate_counts
     if threads is None:
-        threads = min(os.cpu_count() or 8, CPU_BASELINE_THREADS)
+        threads = min(usable_cpus(), CPU_BASELINE_THREADS)
     prev = torch.get_num_threads()
     torch.set_num_threads(int(threads))
     try:
@@ -298,7 +370,7 @@ def cpu_baseline(cfg, sd, reps=5, steps_per_rep=16, threads=None):
                 "min_s": round(min(times), 3), "max_s": round(max(times), 3),
                 "sample": "2 warm-up calls, then %d timings of %d reference calls of b=8 pairs each (%d calls; fwd+loss+bwd, f32, "
                           "%d torch threads of %d host threads); value = %d pairs / median %.2f s (min %.2f, max %.2f)"
-                          % (reps, calls, calls * reps, threads, os.cpu_count() or 0, pairs, med, min(times), max(times))}
+                          % (reps, calls, calls * reps, threads, usable_cpus(), pairs, med, min(times), max(times))}
     finally:
         torch.set_num_threads(prev)
 
@@ -407,20 +479,23 @@ def run_rank(args):
         # initialisation, whatever --warmup / --steps are.
         opt.param_groups[0]["lr"] = BENCH_LR_SCALE * 1e-5 * min(1.0, (380.0 / max(scene0.n_steps, 1)) ** 2)
 
+        last = {}
+
         def step():
             if args.forward_only:
-                model.forward_pairs(scene0 if args.cached_scene else flatten_scene(cfg, batch, dev))
+                last["out"] = model.forward_pairs(scene0 if args.cached_scene else flatten_scene(cfg, batch, dev))
                 return None
             return train_minibatch(model, batch, opt, reducer=reducer, scene=scene0 if args.cached_scene else None, streams=args.streams)
 
-        eng.timers = {}
+        # per-kernel HIP events (engine.timers) only for --full: a plain run times the step without them
+        eng.timers = {} if args.full else None
         eng._xw = None
         first_loss = None
         for _ in range(warmup):
             l0 = step()
             if first_loss is None and l0 is not None:
                 first_loss = float(l0)
-        eng.timers = {}
+        eng.timers = {} if args.full else None
         torch.cuda.reset_peak_memory_stats(dev)
         barrier()
         reducer.pop_exposed_ms()
@@ -430,13 +505,14 @@ def run_rank(args):
             loss = step()
         barrier()
         dt = time.time() - t0
-        kern = {name: float(np.mean([a.elapsed_time(b) for a, b in evs])) for name, evs in eng.timers.items()}
+        kern = {name: float(np.mean([a.elapsed_time(b) for a, b in evs])) for name, evs in (eng.timers or {}).items()}
+        outputs = last.get("out") if args.forward_only else model.last_outputs
         xw = getattr(eng, "_xw", None)
         n_x = int(xw[1][-1]) if xw is not None else 0
         exp_bytes = None
         Pn = scene0.n_pairs
         one_group = eng.ws.bufs["xw_pixrect"].numel() >= Pn if "xw_pixrect" in eng.ws.bufs else False    # image groups / lanes: per-group tables
-        if xw is not None and "expand_dense" in kern and one_group and not args.forward_only and (args.streams or 1) == 1:
+        if args.full and xw is not None and "expand_dense" in kern and one_group and not args.forward_only and (args.streams or 1) == 1:
             exp_bytes = expansion_bytes(eng.ws.bufs["xw_pixrect"][:Pn].cpu().numpy(), scene0.sub_idx.cpu().numpy(), scene0.obj_idx.cpu().numpy(),
                                         int(scene0.obj_img.shape[0]), bf16_copy="z_pad_bf" in eng.ws.bufs and
                                         eng.ws.bufs["z_pad_bf"].numel() >= (Pn + 1) * 18 * 18 * 512)
@@ -445,10 +521,16 @@ def run_rank(args):
                     shared=xw is not None, n_x=n_x, n_list=n_list, n_obj=int(scene0.obj_img.shape[0]),
                     linear=getattr(eng, "_xw_linear", None) if xw is not None else None,
                     exposed_ms=reducer.pop_exposed_ms() / max(steps, 1), exp_bytes=exp_bytes,
-                    peak_gb=torch.cuda.max_memory_allocated(dev) / 1e9)
+                    peak_gb=torch.cuda.max_memory_allocated(dev) / 1e9, outputs=outputs)
 
     m = measure(batch, args.steps, args.warmup)
     P, loss, first_loss, kern = m["P"], m["loss"], m["first_loss"], m["kern"]
+    if args.dump_outputs:
+        if hasattr(opt, "wait_gathers"):
+            opt.wait_gathers()                               # a deferred all-gather may still be writing fc1.weight
+        if rank == 0:
+            write_outputs(args.dump_outputs, loss, m["outputs"], None if args.forward_only else model)
+    m["outputs"] = None
     t = torch.tensor([m["dt"]], device=dev, dtype=torch.float64)
     rank_ms = torch.zeros(world, device=dev, dtype=torch.float64)
     rank_ms[rank] = m["dt"] / args.steps * 1e3
@@ -465,16 +547,16 @@ def run_rank(args):
     # same step on ONE stream (after the timed region; 1 warm-up + 2 steps) gives them; rank 0, N = 1 only.
     kern_1s = None
     from scene_graph_commonsense_amd import engine as _engine_mod
-    if world == 1 and not args.forward_only and _engine_mod.TUNING.bwd_streams:
+    if args.full and world == 1 and not args.forward_only and _engine_mod.TUNING.bwd_streams:
         with _engine_mod.tuning(bwd_streams=False):
             kern_1s = measure(batch, 2, 1)["kern"]
-    elif not args.forward_only:
+    elif args.full and not args.forward_only:
         kern_1s = kern
 
     # ---- box-size sensitivity (N=1): the same step on scaled boxes - the pair-specific share of conv3 / fc1, hence the step time
     # and the workspace, depend on how much the objects' window rectangles overlap; the reference's cost does not
     sensitivity = None
-    if world == 1 and not args.no_sensitivity and not args.forward_only and args.box_scale == 1.0 and args.box_dist == "survey":
+    if args.full and world == 1 and not args.no_sensitivity and not args.forward_only and args.box_scale == 1.0 and args.box_dist == "survey":
         sensitivity = []
         from scene_graph_commonsense_amd.synthetic import with_vg_like_boxes
         vg = "raw boxes with assumed VG-like marginals (median area %d %% of the image) through the reference's box pipeline"
@@ -497,8 +579,8 @@ def run_rank(args):
     # multiply-adds are SURVEY 8d's 8.99 GFLOP per ordered pair, so its rate is what "fraction of the MFMA peak on the survey's flop
     # count" honestly means (``survey_equivalent_tflops`` of the headline exceeds the peak because most of that work is not executed)
     survey_pass = None
-    if world == 1 and not args.no_sensitivity and not args.forward_only and args.box_scale == 1.0 and args.box_dist == "survey" \
-            and (args.streams or 1) == 1 and args.images * args.objects <= 1024:
+    if args.full and world == 1 and not args.no_sensitivity and not args.forward_only and args.box_scale == 1.0 \
+            and args.box_dist == "survey" and (args.streams or 1) == 1 and args.images * args.objects <= 1024:
         eng.ws.bufs.clear()
         model._weights_version = None
         torch.cuda.empty_cache()
@@ -640,10 +722,13 @@ def run_rank(args):
         if world > 1:
             out["dp_mode"] = args.dp_mode if not args.torch_sgd else "allreduce"
             out["exposed_comm_ms"] = round(m["exposed_ms"], 3)      # rank 0: time its compute stream waited for collectives, per step
-        if two_streams:
+        if not args.full:
+            # a plain run: the headline, its configuration and this run's own bookkeeping; the analysis fields are --full's
+            out = {k: v for k, v in out.items() if k in PLAIN_FIELDS}
+        elif two_streams:
             out["kernels_note"] = ("backward launches run on two streams and overlap: their HIP-event durations are not kernel times and "
                                    "are omitted (SGC_BWD_STREAMS=0 for single-stream per-kernel numbers, as in profiles/)")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, sd)
         print(json.dumps(out), flush=True)
     if world > 1:

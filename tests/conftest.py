@@ -29,9 +29,10 @@ def pytest_collection_modifyitems(config, items):
     items.sort(key=rank)
     if any(it.get_closest_marker("gpu") for it in items):
         # in-process oracle calls (b <= 8 pairs per reference call) are FASTEST on ~32 threads of the GPU box's 256
-        # (profiles/r04_oracle_threads.txt: 30 pairs/s on 32 threads, 11 on 128); the pool's jobs take 8 x 8 more
+        # (profiles/r04_oracle_threads.txt: 30 pairs/s on 32 threads, 11 on 128), never more than this process may use
         import torch
-        torch.set_num_threads(min(32, os.cpu_count() or 8))
+        from tests.oracle_pool import usable_cpus
+        torch.set_num_threads(min(32, usable_cpus()))
     kinds = {}
     for it in items:
         m = it.get_closest_marker("oracle_jobs")

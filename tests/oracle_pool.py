@@ -26,18 +26,45 @@ _order = []           # submission order of queued jobs
 _root = None
 
 
+# Every job is a process that may count as holding the GPU although the pool hides the devices from it; the suite's widest test
+# already holds 9 (this process + the 8 ranks of tests/test_bench_gpu.py) and the whole suite keeps to 16 such processes at a time.
+MAX_JOBS = 6
+
+
+def usable_cpus():
+    """Host threads this process may really use: ``os.cpu_count()`` counts the whole machine, a job is often given fewer
+    (affinity mask, cgroup CPU quota, OMP_NUM_THREADS set by whoever started it)."""
+    n = os.cpu_count() or 8
+    try:
+        n = min(n, len(os.sched_getaffinity(0)))
+    except (AttributeError, OSError):
+        pass
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(int(quota) // int(period))))
+    except (OSError, ValueError):
+        pass
+    try:
+        n = min(n, int(os.environ.get("OMP_NUM_THREADS", "") or n))
+    except ValueError:
+        pass
+    return max(1, n)
+
+
 def _plan():
     """(concurrent jobs, torch threads per job).  One oracle call of b = 8 pairs does not scale with threads - measured on the GPU
     box's 256 host threads (tools/oracle_threads.py -> profiles/r04_oracle_threads.txt): 1 process x 8 / 32 / 128 threads = 20 / 30 /
-    11 pairs/s, 8 processes x 8 threads = 52 pairs/s in total - so a many-core host runs several narrow jobs side by side."""
-    n = os.cpu_count() or 8
+    11 pairs/s, 8 processes x 8 threads = 52 pairs/s in total - so a host with 16 or more usable threads runs several narrow jobs
+    side by side, at most MAX_JOBS of them."""
+    n = usable_cpus()
     env = os.environ.get("SGC_ORACLE_POOL")              # "jobs x threads", e.g. 6x16
     if env:
         j, t = env.lower().split("x")
-        return int(j), int(t)
-    if n <= 16:
+        return min(int(j), MAX_JOBS), int(t)
+    if n < 16:
         return 1, n
-    return min(8, n // 8), 8
+    return min(MAX_JOBS, n // 8), 8
 
 
 def _tmp_root():

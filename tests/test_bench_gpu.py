@@ -1,4 +1,5 @@
-"""bench.py's contract: one JSON line, n_gpus equal to --gpus, roofline object present, refusals.  The multi-rank test runs it as the
+"""bench.py's contract: one JSON line, n_gpus equal to --gpus, roofline object present with --full, headline only without it,
+outputs written by --dump-outputs, refusals.  The multi-rank test runs it as the
 driver does - a subprocess that launches its ranks; the single-rank line and the two refusals call ``bench.main(argv)`` in this
 process (same entry point and argument parsing; a fresh interpreter + ``import torch`` costs 10 s on a quiet box and has been seen to
 take over a minute on a busy one, four times per suite)."""
@@ -33,7 +34,7 @@ def _main_in_process(capsys, monkeypatch, *flags, env=None):
 def test_bench_single_rank_line(capsys, monkeypatch):
     import gc
     import torch
-    code, text = _main_in_process(capsys, monkeypatch, "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline")
+    code, text = _main_in_process(capsys, monkeypatch, "--gpus", "1", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full")
     gc.collect()
     torch.cuda.empty_cache()                             # the sensitivity points grew a 100+ GB workspace in this process
     assert code in (None, 0), text[-3000:]
@@ -78,6 +79,31 @@ def test_bench_single_rank_line(capsys, monkeypatch):
     assert 0.2 < out["survey_flops_step_frac"] < 1 and out["survey_flops_step_frac"] == sp["survey_flops_step_frac"]
     assert sp["ms_per_step"] > out["ms_per_step"]                      # the per-pair form is slower than the shipped step (5x when both are warm)
     assert out["survey_equivalent_tflops"] > 0
+
+
+def test_bench_plain_line_and_dumped_outputs(capsys, monkeypatch, tmp_path):
+    """Without --full the line holds the headline and its configuration only (no per-kernel timers, no extra passes); --dump-outputs
+    writes the last timed step's loss, pair outputs and updated parameters as float32 / float64 .npy files, at most 64 MB."""
+    import gc
+    import numpy as np
+    import torch
+    code, text = _main_in_process(capsys, monkeypatch, "--gpus", "1", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path))
+    gc.collect()
+    torch.cuda.empty_cache()
+    assert code in (None, 0), text[-3000:]
+    lines = [l for l in text.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, text
+    out = json.loads(lines[0])
+    assert out["n_gpus"] == 1 and out["steps"] == 2 and out["unit"] == "pairs/s" and out["higher_is_better"] is True
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["dtype"] and out["metric"].startswith("ordered object-pairs/sec")
+    import bench
+    assert set(out) <= set(bench.PLAIN_FIELDS)
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert {"loss", "out_relation", "out_connectivity", "out_hidden", "param_fc1.weight", "param_conv3_1.weight"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert float(files["loss"][0]) == out["loss"] and np.isfinite(files["out_relation"]).all()
+    assert files["out_relation"].shape == (32256, 50) and files["param_fc1.weight"].shape == (bench.DUMP_SAMPLE,)
 
 
 def test_bench_refuses_a_world_size_that_is_not_gpus(capsys, monkeypatch):

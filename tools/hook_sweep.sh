@@ -4,7 +4,7 @@
 #   SGC_EXPERIMENTS=1 python -m scene_graph_commonsense_amd.build --force
 #   bash tools/hook_sweep.sh        -> one line per run: hook setting, ms/step, per-kernel ms
 run() {
-    env SGC_EXPERIMENTS=1 "$@" python bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-sensitivity 2>/dev/null | python -c "
+    env SGC_EXPERIMENTS=1 "$@" python bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --no-sensitivity 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels_ms']
 print('%-28s %7.2f ms  conv3 f/d/w %.2f %.2f %.2f  fc1 f/d/w %.2f %.2f %.2f  expand %.2f unpool %.2f contract %.2f' % ('$*', d['ms_per_step'], k['conv3_fwd'], k['conv3_dgrad'], k['conv3_wgrad'], k['fc1_fwd'], k['fc1_dgrad'], k['fc1_wgrad'], k['expand_dense'], k['unpool'], k['contract']))"

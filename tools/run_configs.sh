@@ -3,7 +3,7 @@
 #   bash tools/run_configs.sh > profiles/rNN_configs.txt
 run() {
     label=$1; shift
-    env "$@" python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-sensitivity ${ARGS} 2>/dev/null | python -c "
+    env "$@" python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline --no-sensitivity ${ARGS} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('%-62s %8.2f ms/step  %9.0f pairs/s  frac %.3f  step_frac %s  peak %.1f GB' % ('$label', d['ms_per_step'], d['value'], (d['roofline'] or {}).get('frac', 0) if d['roofline'] else 0, (d['roofline'] or {}).get('step_frac'), d['peak_memory_gb']))"
