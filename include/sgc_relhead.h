@@ -298,6 +298,21 @@ int sgc_fc2_labels_relu(const void* h1, const void* w2m, const float* b, const f
 int sgc_bayes_head(const float* p, const float* Wt, const float* bias, int n_pairs, int ng, int np, int ns, int hier, float T1, float T2,
                    float T3, float* rel, float* sup, float* conn, float* cand_conf, int* cand_pred, const unsigned char* iou_mask, void* stream);
 
+/* Plug-and-play BayesianHead on features of any width   (model.py:9-34: fc3_1 / fc3_2 / fc3_3 / fc5 on the same h, log_softmax of
+ * fc5, three log_softmax(fc3_k(h) / T_k) + super[:, k]; the reference reads h once per nn.Linear, this reads it once).
+ * h [M][D] f32 (any D >= 1, M >= 0), W [64][D] f32 = the packed rows (R = ng + np + ns fine-relation rows, then the three fc5 rows,
+ * zero rows up to 64; ng + np + ns + 3 <= 64), bias [64].  rel [M][R] (the three blocks side by side), sup [M][3]. */
+int sgc_bayes_head_any(const float* h, const float* W, const float* bias, int M, int D, int ng, int np, int ns, float T1, float T2,
+                       float T3, float* rel, float* sup, void* stream);
+/* Its backward (autograd of model.py:24-34; one pass over h): g_rel [M][R] / g_sup [M][3] = dL/d(rel) / dL/d(sup) (either may be NULL =
+ * zero); rel / sup = the forward's outputs (the softmaxes are rebuilt as exp(rel_k - sup[k]) and exp(sup), no logits are kept).
+ * dh [M][D] = dz W (may be NULL); part [ceil(M/256)][64][D+1] (may be NULL): per 256-row chunk dW = dz^T h (columns 0..D-1) and
+ * db = sum dz (column D), where dz [M][64] = dL/d(packed logits). */
+int sgc_bayes_head_any_bwd(const float* h, const float* W, const float* rel, const float* sup, const float* g_rel, const float* g_sup,
+                           int M, int D, int ng, int np, int ns, float T1, float T2, float T3, float* dh, float* part, void* stream);
+/* out [64][D+1] = sum of the n_part partials of sgc_bayes_head_any_bwd in partial order (the same bits on every run; no atomics). */
+int sgc_bayes_head_any_wreduce(const float* part, int n_part, int D, float* out, void* stream);
+
 /* Per-image stable descending top-K over the accumulated candidates   (evaluator.py:292-316: confidence += connectivity, argsort, top 100).
  * conf [n_cand] f32 (already including the connectivity term), seg_ptr [n_img+1]; out_idx [n_img][K] image-local candidate
  * indices (-1 padded), out_count [n_img]. */

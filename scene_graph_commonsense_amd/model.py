@@ -13,12 +13,15 @@ There is no CPU or eager-PyTorch fallback: the HIP extension must load and the m
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, List, Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
+from . import _lib
 from .engine import PairOutputs, RelHeadEngine, make_engine
 from .pairs import DeviceScene, pair_targets_fast, super_multihot
 from .synthetic import HeadConfig, predicate_counts
@@ -533,37 +536,114 @@ class FlatRelationClassifier(_RelationBase):
         return rel, conn, pred, pred_aug
 
 
+HEAD_ANY_ROWS = 256          # rows of h per dW / db partial of sgc_bayes_head_any_bwd (csrc/kernels_head.hip)
+
+
+def _head_any_forward(head, h, W, b):
+    """rel [M,R], sup [M,3] of ``sgc_bayes_head_any`` on f32 contiguous h [M,D] and the packed W [64,D] / b [64]."""
+    lib = _lib.load()
+    M, D = h.shape
+    rel = torch.empty(M, head.ng + head.np_ + head.ns, dtype=torch.float32, device=h.device)
+    sup = torch.empty(M, 3, dtype=torch.float32, device=h.device)
+    f = ctypes.c_float
+    _lib.check(lib.sgc_bayes_head_any(_lib.ptr(h), _lib.ptr(W), _lib.ptr(b), M, D, head.ng, head.np_, head.ns, f(head.T1),
+                                      f(head.T2), f(head.T3), _lib.ptr(rel), _lib.ptr(sup), _lib.stream_ptr()), "sgc_bayes_head_any")
+    return rel, sup
+
+
+class _BayesHeadFunction(torch.autograd.Function):
+    """``BayesianHead.forward`` (reference ``model.py:24-34``) as ONE autograd node: forward = ``sgc_bayes_head_any``, backward =
+    ``sgc_bayes_head_any_bwd`` (dh and per-chunk dW / db partials from the saved outputs) + the fixed-order partial sum, split back
+    onto fc3_1 / fc3_2 / fc3_3 / fc5.  Inputs: h (f32, contiguous), the eight parameters, the module."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, w3, b3, w5, b5, head):
+        W, b = head._packed(h.device)
+        rel, sup = _head_any_forward(head, h, W, b)
+        ctx.save_for_backward(h, rel, sup, W)
+        ctx.head = head
+        ctx.set_materialize_grads(False)
+        return rel, sup
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_rel, g_sup):
+        h, rel, sup, W = ctx.saved_tensors
+        head = ctx.head
+        need_h, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:9])
+        M, D = h.shape
+        lib = _lib.load()
+        g_rel = None if g_rel is None else g_rel.to(torch.float32).contiguous()
+        g_sup = None if g_sup is None else g_sup.to(torch.float32).contiguous()
+        dh = torch.empty_like(h) if need_h else None
+        n_part = (M + HEAD_ANY_ROWS - 1) // HEAD_ANY_ROWS
+        part = torch.empty(n_part, 64, D + 1, dtype=torch.float32, device=h.device) if need_w else None
+        f = ctypes.c_float
+        _lib.check(lib.sgc_bayes_head_any_bwd(_lib.ptr(h), _lib.ptr(W), _lib.ptr(rel), _lib.ptr(sup), _lib.ptr(g_rel), _lib.ptr(g_sup),
+                                              M, D, head.ng, head.np_, head.ns, f(head.T1), f(head.T2), f(head.T3), _lib.ptr(dh),
+                                              _lib.ptr(part), _lib.stream_ptr()), "sgc_bayes_head_any_bwd")
+        grads = [None] * 8
+        if need_w:
+            dwb = torch.empty(64, D + 1, dtype=torch.float32, device=h.device)
+            _lib.check(lib.sgc_bayes_head_any_wreduce(_lib.ptr(part), n_part, D, _lib.ptr(dwb), _lib.stream_ptr()),
+                       "sgc_bayes_head_any_wreduce")
+            lo = 0
+            for k, rows in enumerate((head.ng, head.np_, head.ns, 3)):
+                if ctx.needs_input_grad[1 + 2 * k]:
+                    grads[2 * k] = dwb[lo:lo + rows, :D].contiguous()
+                if ctx.needs_input_grad[2 + 2 * k]:
+                    grads[2 * k + 1] = dwb[lo:lo + rows, D].contiguous()
+                lo += rows
+        return (dh, *grads, None)
+
+
 class BayesianHead(nn.Module):
-    """Plug-and-play hierarchical head on ``[M,512]`` features - drop-in for reference ``model.py:9-34``."""
+    """Plug-and-play hierarchical head on ``[M, input_dim]`` features - drop-in for reference ``model.py:9-34``, trainable: the
+    loss flows back through it (into fc3_1 / fc3_2 / fc3_3 / fc5 and into whatever produced h)."""
 
     def __init__(self, input_dim=512, num_geometric=15, num_possessive=11, num_semantic=24, T1=1, T2=1, T3=1):
         super().__init__()
-        if input_dim != 512:
-            raise NotImplementedError("the head kernel is specialised to 512 input features")
+        if num_geometric + num_possessive + num_semantic + 3 > 64:
+            raise NotImplementedError("the head kernel packs the fine relations and the 3 super logits into 64 output rows: "
+                                      "num_geometric + num_possessive + num_semantic + 3 must be <= 64")
         self.fc3_1 = nn.Linear(input_dim, num_geometric)
         self.fc3_2 = nn.Linear(input_dim, num_possessive)
         self.fc3_3 = nn.Linear(input_dim, num_semantic)
         self.fc5 = nn.Linear(input_dim, 3)
         self.T1, self.T2, self.T3 = T1, T2, T3
         self.ng, self.np_, self.ns = num_geometric, num_possessive, num_semantic
-        self._eng = None
+        self._pack_key, self._pack = None, None
+
+    def _params(self):
+        return (self.fc3_1.weight, self.fc3_1.bias, self.fc3_2.weight, self.fc3_2.bias, self.fc3_3.weight, self.fc3_3.bias,
+                self.fc5.weight, self.fc5.bias)
+
+    def _packed(self, device):
+        """W [64, D] / b [64] f32 on ``device``: the four layers' rows stacked, zero-padded; rebuilt only when a parameter changed
+        (its ``_version`` counts in-place updates such as an optimizer step) or was replaced."""
+        ps = self._params()
+        key = (device,) + tuple((p.data_ptr(), p._version) for p in ps)
+        if key != self._pack_key:
+            with torch.no_grad():
+                rows = torch.cat(ps[0::2]).to(device, torch.float32)
+                W = torch.zeros(64, rows.shape[1], dtype=torch.float32, device=device)
+                W[:rows.shape[0]] = rows
+                b = torch.zeros(64, dtype=torch.float32, device=device)
+                b[:rows.shape[0]] = torch.cat(ps[1::2]).to(device, torch.float32)
+            self._pack_key, self._pack = key, (W, b)
+        return self._pack
 
     def forward(self, h):
-        dev = h.device
-        if dev.type != "cuda":
+        if h.device.type != "cuda":
             raise RuntimeError("BayesianHead runs only on a GPU through its HIP kernel (no CPU fallback)")
-        cfg = HeadConfig(num_geometric=self.ng, num_possessive=self.np_, num_semantic=self.ns)
-        if self._eng is None or self._eng.device != dev:
-            self._eng = RelHeadEngine(cfg, dev)
-        eng = self._eng
-        eng.T = (float(self.T1), float(self.T2), float(self.T3))
-        with torch.no_grad():
-            rows = torch.cat([self.fc3_1.weight, self.fc3_2.weight, self.fc3_3.weight, self.fc5.weight])
-            Wc = torch.zeros(64, 512, device=dev)
-            Wc[:rows.shape[0]] = rows
-            bc = torch.zeros(64, device=dev)
-            bc[:rows.shape[0]] = torch.cat([self.fc3_1.bias, self.fc3_2.bias, self.fc3_3.bias, self.fc5.bias])
-            eng.w["head_wt"], eng.w["head_b"] = Wc.t().contiguous(), bc
-            out = eng.head(h.float().contiguous().view(-1), int(h.shape[0]))
-        rel = out.relation
-        return rel[:, :self.ng], rel[:, self.ng:self.ng + self.np_], rel[:, self.ng + self.np_:], out.super_relation
+        x = h.to(torch.float32).contiguous()        # autograd hands the gradient back to h in h's own dtype
+        with torch.cuda.device(h.device):
+            # The node is recorded when h carries a gradient (the head behind a host model).  Features that do not (a plain tensor)
+            # give plain outputs, which callers may turn into arrays; to train the head alone on fixed features, pass
+            # h.requires_grad_() - or call _BayesHeadFunction directly, which then computes dW / db only.
+            if torch.is_grad_enabled() and x.requires_grad:
+                rel, sup = _BayesHeadFunction.apply(x, *self._params(), self)
+            else:
+                rel, sup = _head_any_forward(self, x, *self._packed(h.device))
+        ng, npos = self.ng, self.np_
+        return rel[:, :ng], rel[:, ng:ng + npos], rel[:, ng + npos:], sup
