@@ -312,6 +312,27 @@ int sgc_bayes_head_any_bwd(const float* h, const float* W, const float* rel, con
                            int M, int D, int ng, int np, int ns, float T1, float T2, float T3, float* dh, float* part, void* stream);
 /* out [64][D+1] = sum of the n_part partials of sgc_bayes_head_any_bwd in partial order (the same bits on every run; no atomics). */
 int sgc_bayes_head_any_wreduce(const float* part, int n_part, int D, float* out, void* stream);
+/* The class-weighted hierarchical NLL of the plug-and-play head, fused into its forward   (train_utils.py:116-157 with the criteria of
+ * train_test.py:105-117: NLLLoss on the super category of the connected rows plus, per super category, the class-weighted NLLLoss of
+ * the rows whose target lies in it; about twenty launches and a nonzero per block in the reference).
+ * target [M] int64 (target_is_int64 != 0) or int32: a value in [0, R) is the row's relation, any other value skips the row
+ * ("no relation"; the reference selects the connected rows, :118-125); class_weight [R] f32 or NULL = ones.
+ * norm [4] (out): |C| and the three sums of class weights over the rows of each block, by a fixed-order reduction on the device.
+ * dz [M][64] (out, may be NULL): dL/d(packed logits), formed from the logits (no log-probs are written);
+ * loss_part [ceil(M/32)] double (scratch: one loss partial per workgroup); loss [1] (out) = their fixed-order sum.  With no connected
+ * row the loss is exactly 0 and dz is zero (:121-122). */
+int sgc_bayes_head_any_loss(const float* h, const float* W, const float* bias, const void* target, int target_is_int64,
+                            const float* class_weight, int M, int D, int ng, int np, int ns, float T1, float T2, float T3, float* norm,
+                            float* dz, double* loss_part, float* loss, void* stream);
+/* Its backward (autograd of train_utils.py:131-157 through model.py:24-34): the second stage of sgc_bayes_head_any_bwd fed g[0] * dz
+ * from memory, g [1] = dL/d(loss) on the device.  dh [M][D] (may be NULL), part [ceil(M/256)][64][D+1] (may be NULL) as there. */
+int sgc_bayes_head_any_loss_bwd(const float* h, const float* W, const float* dz, const float* g, int M, int D, float* dh, float* part,
+                                void* stream);
+/* The three ranked candidates per row of the plug-and-play head   (evaluator.py:160-174: per super category the maximum log-prob of
+ * the block and its first arg-max plus the block offset; Evaluator_Top3 :646-648 takes their maximum).  Same logits and log-probs as
+ * sgc_bayes_head_any, so cand_conf [M][3] is bit for bit the block maxima of its rel; cand_pred [M][3] int32, sup [M][3]. */
+int sgc_bayes_head_any_candidates(const float* h, const float* W, const float* bias, int M, int D, int ng, int np, int ns, float T1,
+                                  float T2, float T3, float* cand_conf, int* cand_pred, float* sup, void* stream);
 
 /* Per-image stable descending top-K over the accumulated candidates   (evaluator.py:292-316: confidence += connectivity, argsort, top 100).
  * conf [n_cand] f32 (already including the connectivity term), seg_ptr [n_img+1]; out_idx [n_img][K] image-local candidate

@@ -8,6 +8,10 @@
 //             h is read once (the reference reads it once per nn.Linear).
 //   backward  dz from the saved outputs (softmax_k = exp(rel_k - sup[k]), softmax(s) = exp(sup)), then dh = dz W and per-row-chunk
 //             partials of dW = dz^T h, db = sum dz in one pass; the partials are summed by a separate fixed-order reduce.
+//
+// The forward's main loop has two more epilogues on the same logit bits: the class-weighted hierarchical NLL (train_utils.py:116-157)
+// with dz = dL/dz formed straight from the logits, which the backward then reads from memory instead of rebuilding it, and the three
+// ranked candidates per row (evaluator.py:160-174).
 #include "common.h"
 
 namespace {
@@ -45,14 +49,27 @@ __device__ __forceinline__ f32x4 ld4(const float* row, int k, int D) {
 
 struct AnyFwdParams {
     const float* h; const float* W; const float* b; int M; int D; int ng, np, ns; float T1, T2, T3; float* rel; float* sup;
+    // EPI_LOSS: target [M] (int64 when tgt64, else int32), cw [R] or null, norm [4], dz [M][64] or null, loss_part [gridDim.x]
+    const void* target; int tgt64; const float* cw; const float* norm; float* dz; double* loss_part;
+    // EPI_CAND: cand_conf / cand_pred [M][3] (sup is written too)
+    float* cand_conf; int* cand_pred;
 };
+
+enum { EPI_LOGPROB = 0, EPI_LOSS = 1, EPI_CAND = 2 };
+
+// Row m's target, or -1 for a row the loss skips (negative = "no relation"; a value past R is skipped too, never indexed with).
+__device__ __forceinline__ int head_target(const void* target, int tgt64, long m, int R) {
+    const long long t = tgt64 ? static_cast<const long long*>(target)[m] : static_cast<const int*>(target)[m];
+    return (t >= 0 && t < R) ? (int)t : -1;
+}
 
 // One workgroup per tile of TM*32 rows.  Wave w takes the k-chunks c = w, w+4, ... of 8 k: lane (i, half) loads h[row i][8c+4half ..
 // +3] and W[n][8c+4half .. +3] as one 16-byte vector each and issues four MFMAs per (row tile, 32 outputs) - the k order inside a
 // chunk is the same permutation for both operands.  The four waves' partial sums meet in LDS and are added in wave order.
-template <int TM, bool VEC>
+// EPI selects what is made of the logits: the module's four log-prob outputs, the hierarchical loss and its dz, or the candidates.
+template <int TM, bool VEC, int EPI>
 __global__ __launch_bounds__(256) void head_any_fwd_kernel(const AnyFwdParams p) {
-    __shared__ float red[ANY_WAVES][TM * 32][64];
+    __shared__ __attribute__((aligned(16))) float red[ANY_WAVES][TM * 32][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int li = lane & 31, lh = lane >> 5;
     const long m0 = (long)blockIdx.x * (TM * 32);
@@ -112,16 +129,45 @@ __global__ __launch_bounds__(256) void head_any_fwd_kernel(const AnyFwdParams p)
     const bool in_sup = lane >= R && lane < R + 3;
     const int seg = lane < p.ng ? 0 : (lane < p.ng + p.np ? 1 : 2);
     const float T = seg == 0 ? p.T1 : (seg == 1 ? p.T2 : p.T3);
+    double lsum = 0.0;                                      // EPI_LOSS: this wave's loss terms, in row order
+    float inv_c = 0.f, wsum[3] = {1.f, 1.f, 1.f};
+    if (EPI == EPI_LOSS) {
+        inv_c = p.norm[0] > 0.f ? 1.f / p.norm[0] : 0.f;
+        wsum[0] = p.norm[1]; wsum[1] = p.norm[2]; wsum[2] = p.norm[3];
+    }
     for (int rr = w; rr < TM * 32; rr += ANY_WAVES) {
         const long m = m0 + rr;
         if (m >= p.M) break;                                // wave-uniform
         const float z = (((red[0][rr][lane] + red[1][rr][lane]) + red[2][rr][lane]) + red[3][rr][lane]) + bias;
         const float smax = hmax(z, in_sup);
         const float ssum = hsum(expf(z - smax), in_sup);
+        if (EPI == EPI_LOSS) {
+            // L = a * -sup[k] + b * -rel_k[t - off_k] with a = 1/|C|, b = w[t] / sum_{C_k} w (train_utils.py:131-151), so
+            // dz_sup = (a + b)(softmax(z_sup) - e_k), dz_k = (b / T_k)(softmax(z_k / T_k) - e_t), everything else zero
+            const int t = head_target(p.target, p.tgt64, m, R);                // wave-uniform
+            float v = 0.f;
+            if (t >= 0) {
+                const int k = t < p.ng ? 0 : (t < p.ng + p.np ? 1 : 2);
+                const float a = inv_c, b = (p.cw ? p.cw[t] : 1.f) / (k == 0 ? wsum[0] : (k == 1 ? wsum[1] : wsum[2]));
+                const float slog = __shfl(z - smax - logf(ssum), R + k);
+                const bool in = lane < R && seg == k;
+                const float x = z / T;
+                const float mx = hmax(x, in);
+                const float e = expf(x - mx);
+                const float sm = hsum(e, in);
+                const float rel_t = __shfl(x - mx - logf(sm) + slog, t);       // the value forward() gives at the target
+                if (in) v = (b / T) * (e / sm - (lane == t ? 1.f : 0.f));
+                if (in_sup) v = (a + b) * (expf(z - smax) / ssum - (lane - R == k ? 1.f : 0.f));
+                lsum += (double)(-(a * slog) - b * rel_t);
+            }
+            if (p.dz) p.dz[m * 64 + lane] = v;
+            continue;
+        }
         const float slog = z - smax - logf(ssum);          // valid on the three super lanes
         if (in_sup) p.sup[m * 3 + (lane - R)] = slog;
         const float x = z / T;
-        float out = 0.f;
+        float out = 0.f, cbest = 0.f;
+        int cpred = 0;
 #pragma unroll
         for (int sg = 0; sg < 3; ++sg) {
             const bool in = lane < R && seg == sg;
@@ -129,14 +175,76 @@ __global__ __launch_bounds__(256) void head_any_fwd_kernel(const AnyFwdParams p)
             const float sm = hsum(expf(x - mx), in);
             const float sl = __shfl(slog, R + sg);
             if (in) out = x - mx - logf(sm) + sl;
+            if (EPI == EPI_CAND) {
+                // evaluator.py:160-174: the block's maximum and its first arg-max.  out rises with x, so its maximum is out where
+                // x == mx, the same operations on x - mx = 0: no second reduction.  Lanes of equal out may differ in x: ballot on out.
+                const float best = 0.f - logf(sm) + sl;
+                const unsigned long long hit = __ballot(in && out == best);
+                if (lane == sg) {
+                    cbest = best;
+                    cpred = hit ? __ffsll(hit) - 1 : (sg == 0 ? 0 : (sg == 1 ? p.ng : p.ng + p.np));
+                }
+            }
         }
-        if (lane < R) p.rel[m * R + lane] = out;
+        if (EPI == EPI_CAND && lane < 3) {
+            p.cand_conf[m * 3 + lane] = cbest;
+            p.cand_pred[m * 3 + lane] = cpred;
+        }
+        if (EPI == EPI_LOGPROB && lane < R) p.rel[m * R + lane] = out;
     }
+    if (EPI == EPI_LOSS) {                                  // one partial per workgroup: the four waves' sums in wave order
+        __syncthreads();                                    // red is read no more
+        double* ws = reinterpret_cast<double*>(&red[0][0][0]);
+        if (lane == 0) ws[w] = lsum;
+        __syncthreads();
+        if (threadIdx.x == 0) p.loss_part[blockIdx.x] = ((ws[0] + ws[1]) + ws[2]) + ws[3];
+    }
+}
+
+// norm[0] = |C| (rows with a target in [0, R)), norm[1..3] = sum of w[target] over the rows of each block.  One workgroup: thread i
+// adds rows i, i + 1024, ... in order, then a fixed tree over the threads, all in double - the same bits on every run.
+__global__ __launch_bounds__(1024) void head_loss_norm_kernel(const void* target, int tgt64, const float* cw, int M, int ng, int np,
+                                                              int ns, float* norm) {
+    __shared__ double acc[4][1024];
+    const int R = ng + np + ns;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (long m = threadIdx.x; m < M; m += 1024) {
+        const int t = head_target(target, tgt64, m, R);
+        if (t >= 0) {
+            s[0] += 1.0;
+            s[t < ng ? 1 : (t < ng + np ? 2 : 3)] += (double)(cw ? cw[t] : 1.f);
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) acc[q][threadIdx.x] = s[q];
+    __syncthreads();
+    for (int o = 512; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) acc[q][threadIdx.x] += acc[q][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) norm[threadIdx.x] = (float)acc[threadIdx.x][0];
+}
+
+// loss = sum of the n workgroup partials: thread i adds partials i, i + 256, ... in order, then a fixed tree, in double.
+__global__ __launch_bounds__(256) void head_loss_sum_kernel(const double* part, int n, float* loss) {
+    __shared__ double acc[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) s += part[i];
+    acc[threadIdx.x] = s;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) acc[threadIdx.x] += acc[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *loss = (float)acc[0];
 }
 
 struct AnyBwdParams {
     const float* h; const float* W; const float* rel; const float* sup; const float* g_rel; const float* g_sup;
     int M; int D; int ng, np, ns; float T1, T2, T3; float* dh; float* part;
+    const float* dz; const float* g;                        // FROM_DZ: dz [M][64] of the loss forward, g = the scalar dL/d(loss)
 };
 
 // Workgroup (x, y): rows [256x, 256x + 256) of h, 32-column blocks y*4 + w, y*4 + w + 4*gridDim.y, ... of D for wave w.
@@ -144,6 +252,8 @@ struct AnyBwdParams {
 // column block: dh[rows][block] = dz W[:, block] (K = 64, the W operands stay in registers over the row tiles) and
 // dW[:, block] += dz^T h[rows][block] (K = the rows), kept in registers until the block's partial is written.  Workgroup (x, 0)
 // also writes db's partial, sum dz over its rows in row order.  part [gridDim.x][64][D+1], column D = db.
+// FROM_DZ: stage 1 is a copy of g * dz from memory (the fused loss formed dz in its forward).
+template <bool FROM_DZ>
 __global__ __launch_bounds__(256) void head_any_bwd_kernel(const AnyBwdParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* dzs = reinterpret_cast<float*>(smem);            // [ANY_BWD_ROWS][DZ_LD]
@@ -157,10 +267,13 @@ __global__ __launch_bounds__(256) void head_any_bwd_kernel(const AnyBwdParams p)
     const int seg = lane < p.ng ? 0 : (lane < p.ng + p.np ? 1 : 2);
     const float T = seg == 0 ? p.T1 : (seg == 1 ? p.T2 : p.T3);
     const int ks = in_sup ? lane - R : 0;
+    const float gl = FROM_DZ ? *p.g : 0.f;
     for (int i = w; i < ANY_BWD_ROWS; i += ANY_WAVES) {
         const long m = r0 + i;
         float v = 0.f;
-        if (m < p.M) {                                      // wave-uniform
+        if (FROM_DZ) {
+            if (m < p.M) v = gl * p.dz[m * 64 + lane];
+        } else if (m < p.M) {                               // wave-uniform
             const float g = (fine && p.g_rel) ? p.g_rel[m * R + lane] : 0.f;
             const float gs0 = hsum(g, fine && seg == 0), gs1 = hsum(g, fine && seg == 1), gs2 = hsum(g, fine && seg == 2);
             if (fine) v = (g - expf(p.rel[m * R + lane] - p.sup[m * 3 + seg]) * (seg == 0 ? gs0 : (seg == 1 ? gs1 : gs2))) / T;
@@ -243,26 +356,87 @@ __global__ __launch_bounds__(256) void head_any_wreduce_kernel(const float* part
     }
 }
 
+// 64-row tiles halve the W traffic once there are enough of them to fill the chip; 32-row tiles below that
+inline int any_fwd_tile(int M) { return M >= 32768 ? 64 : 32; }
+
+template <int EPI>
+int launch_any_fwd(const AnyFwdParams& p, hipStream_t stream) {
+    const bool vec = p.D % 4 == 0 && ((uintptr_t)p.h & 15) == 0 && ((uintptr_t)p.W & 15) == 0;
+    const int tile = any_fwd_tile(p.M);
+    const dim3 grid((p.M + tile - 1) / tile);
+    if (tile == 64) {
+        if (vec) SGC_LAUNCH((head_any_fwd_kernel<2, true, EPI>), grid, dim3(256), 0, stream, p);
+        else SGC_LAUNCH((head_any_fwd_kernel<2, false, EPI>), grid, dim3(256), 0, stream, p);
+    } else {
+        if (vec) SGC_LAUNCH((head_any_fwd_kernel<1, true, EPI>), grid, dim3(256), 0, stream, p);
+        else SGC_LAUNCH((head_any_fwd_kernel<1, false, EPI>), grid, dim3(256), 0, stream, p);
+    }
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
 
 int sgc_bayes_head_any(const float* h, const float* W, const float* bias, int M, int D, int ng, int np, int ns, float T1, float T2,
                        float T3, float* rel, float* sup, void* stream) {
     if (D < 1 || M < 0 || ng < 0 || np < 0 || ns < 0 || ng + np + ns + 3 > 64) return SGC_ERR_ARG;
     if (M == 0) return SGC_OK;
-    const AnyFwdParams p{h, W, bias, M, D, ng, np, ns, T1, T2, T3, rel, sup};
-    const bool vec = D % 4 == 0 && ((uintptr_t)h & 15) == 0 && ((uintptr_t)W & 15) == 0;
-    // 64-row tiles halve the W traffic once there are enough of them to fill the chip; 32-row tiles below that
-    if (M >= 32768) {
-        const dim3 grid((M + 63) / 64);
-        if (vec) SGC_LAUNCH((head_any_fwd_kernel<2, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else SGC_LAUNCH((head_any_fwd_kernel<2, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    } else {
-        const dim3 grid((M + 31) / 32);
-        if (vec) SGC_LAUNCH((head_any_fwd_kernel<1, true>), grid, dim3(256), 0, (hipStream_t)stream, p);
-        else SGC_LAUNCH((head_any_fwd_kernel<1, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    AnyFwdParams p{};
+    p.h = h; p.W = W; p.b = bias; p.M = M; p.D = D; p.ng = ng; p.np = np; p.ns = ns; p.T1 = T1; p.T2 = T2; p.T3 = T3;
+    p.rel = rel; p.sup = sup;
+    return launch_any_fwd<EPI_LOGPROB>(p, (hipStream_t)stream);
+}
+
+int sgc_bayes_head_any_candidates(const float* h, const float* W, const float* bias, int M, int D, int ng, int np, int ns, float T1,
+                                  float T2, float T3, float* cand_conf, int* cand_pred, float* sup, void* stream) {
+    if (D < 1 || M < 0 || ng < 0 || np < 0 || ns < 0 || ng + np + ns + 3 > 64) return SGC_ERR_ARG;
+    if (M == 0) return SGC_OK;
+    if (!cand_conf || !cand_pred || !sup) return SGC_ERR_ARG;
+    AnyFwdParams p{};
+    p.h = h; p.W = W; p.b = bias; p.M = M; p.D = D; p.ng = ng; p.np = np; p.ns = ns; p.T1 = T1; p.T2 = T2; p.T3 = T3;
+    p.sup = sup; p.cand_conf = cand_conf; p.cand_pred = cand_pred;
+    return launch_any_fwd<EPI_CAND>(p, (hipStream_t)stream);
+}
+
+int sgc_bayes_head_any_loss(const float* h, const float* W, const float* bias, const void* target, int target_is_int64,
+                            const float* class_weight, int M, int D, int ng, int np, int ns, float T1, float T2, float T3, float* norm,
+                            float* dz, double* loss_part, float* loss, void* stream) {
+    if (D < 1 || M < 0 || ng < 0 || np < 0 || ns < 0 || ng + np + ns + 3 > 64) return SGC_ERR_ARG;
+    if (!norm || !loss || (M > 0 && (!target || !loss_part))) return SGC_ERR_ARG;
+    SGC_LAUNCH(head_loss_norm_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, target, target_is_int64, class_weight, M, ng, np, ns,
+               norm);
+    SGC_CHECK_LAUNCH();
+    int n_part = 0;
+    if (M > 0) {
+        AnyFwdParams p{};
+        p.h = h; p.W = W; p.b = bias; p.M = M; p.D = D; p.ng = ng; p.np = np; p.ns = ns; p.T1 = T1; p.T2 = T2; p.T3 = T3;
+        p.target = target; p.tgt64 = target_is_int64; p.cw = class_weight; p.norm = norm; p.dz = dz; p.loss_part = loss_part;
+        n_part = (M + any_fwd_tile(M) - 1) / any_fwd_tile(M);      // one partial per workgroup; at most ceil(M / 32)
+        const int rc = launch_any_fwd<EPI_LOSS>(p, (hipStream_t)stream);
+        if (rc != SGC_OK) return rc;
     }
+    SGC_LAUNCH(head_loss_sum_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, loss_part, n_part, loss);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
+int sgc_bayes_head_any_loss_bwd(const float* h, const float* W, const float* dz, const float* g, int M, int D, float* dh, float* part,
+                                void* stream) {
+    if (D < 1 || M < 0) return SGC_ERR_ARG;
+    if (M == 0 || (!dh && !part)) return SGC_OK;
+    if (!dz || !g) return SGC_ERR_ARG;
+    AnyBwdParams p{};
+    p.h = h; p.W = W; p.M = M; p.D = D; p.dh = dh; p.part = part; p.dz = dz; p.g = g;
+    const int nx = (M + ANY_BWD_ROWS - 1) / ANY_BWD_ROWS;
+    const int nquad = (D + 32 * ANY_WAVES - 1) / (32 * ANY_WAVES);
+    int ny = (512 + nx - 1) / nx;
+    if (ny > nquad) ny = nquad;
+    const int lds = ANY_BWD_ROWS * DZ_LD * 4;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_any_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    SGC_LAUNCH(head_any_bwd_kernel<true>, dim3(nx, ny), dim3(256), lds, (hipStream_t)stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }
@@ -271,14 +445,14 @@ int sgc_bayes_head_any_bwd(const float* h, const float* W, const float* rel, con
                            int M, int D, int ng, int np, int ns, float T1, float T2, float T3, float* dh, float* part, void* stream) {
     if (D < 1 || M < 0 || ng < 0 || np < 0 || ns < 0 || ng + np + ns + 3 > 64) return SGC_ERR_ARG;
     if (M == 0 || (!dh && !part)) return SGC_OK;
-    const AnyBwdParams p{h, W, rel, sup, g_rel, g_sup, M, D, ng, np, ns, T1, T2, T3, dh, part};
+    const AnyBwdParams p{h, W, rel, sup, g_rel, g_sup, M, D, ng, np, ns, T1, T2, T3, dh, part, nullptr, nullptr};
     const int nx = (M + ANY_BWD_ROWS - 1) / ANY_BWD_ROWS;
     const int nquad = (D + 32 * ANY_WAVES - 1) / (32 * ANY_WAVES);       // 128-column groups of D
     int ny = (512 + nx - 1) / nx;                                         // about two workgroups per CU
     if (ny > nquad) ny = nquad;
     const int lds = ANY_BWD_ROWS * DZ_LD * 4;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_any_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    SGC_LAUNCH(head_any_bwd_kernel, dim3(nx, ny), dim3(256), lds, (hipStream_t)stream, p);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(head_any_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    SGC_LAUNCH(head_any_bwd_kernel<false>, dim3(nx, ny), dim3(256), lds, (hipStream_t)stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }

@@ -587,14 +587,69 @@ class _BayesHeadFunction(torch.autograd.Function):
             dwb = torch.empty(64, D + 1, dtype=torch.float32, device=h.device)
             _lib.check(lib.sgc_bayes_head_any_wreduce(_lib.ptr(part), n_part, D, _lib.ptr(dwb), _lib.stream_ptr()),
                        "sgc_bayes_head_any_wreduce")
-            lo = 0
-            for k, rows in enumerate((head.ng, head.np_, head.ns, 3)):
-                if ctx.needs_input_grad[1 + 2 * k]:
-                    grads[2 * k] = dwb[lo:lo + rows, :D].contiguous()
-                if ctx.needs_input_grad[2 + 2 * k]:
-                    grads[2 * k + 1] = dwb[lo:lo + rows, D].contiguous()
-                lo += rows
+            _split_head_grads(ctx, head, dwb, D, grads)
         return (dh, *grads, None)
+
+
+def _split_head_grads(ctx, head, dwb, D, grads):
+    """Rows of dwb [64, D+1] (dW | db of the packed layers) back onto fc3_1 / fc3_2 / fc3_3 / fc5, for the parameters that need one."""
+    lo = 0
+    for k, rows in enumerate((head.ng, head.np_, head.ns, 3)):
+        if ctx.needs_input_grad[1 + 2 * k]:
+            grads[2 * k] = dwb[lo:lo + rows, :D].contiguous()
+        if ctx.needs_input_grad[2 + 2 * k]:
+            grads[2 * k + 1] = dwb[lo:lo + rows, D].contiguous()
+        lo += rows
+
+
+class _BayesHeadLossFunction(torch.autograd.Function):
+    """``BayesianHead.hierarchical_nll`` as ONE autograd node: forward = ``sgc_bayes_head_any_loss`` (normalisers, the head's main loop
+    with the loss epilogue, the partial sum; keeps dz [M,64], writes no log-probs), backward = ``sgc_bayes_head_any_loss_bwd`` on the
+    saved dz and the upstream scalar + the fixed-order partial sum.  Nothing here waits for the device.  Inputs: h (f32, contiguous),
+    the eight parameters, the module, target [M] (int64 / int32, contiguous), class_weight [R] f32 or None."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, w3, b3, w5, b5, head, target, class_weight):
+        W, b = head._packed(h.device)
+        M, D = h.shape
+        dev = h.device
+        lib = _lib.load()
+        need = any(ctx.needs_input_grad[:9])
+        norm = torch.empty(4, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dz = torch.empty(M, 64, dtype=torch.float32, device=dev) if need else None
+        part = torch.empty((M + 31) // 32, dtype=torch.float64, device=dev)
+        f = ctypes.c_float
+        _lib.check(lib.sgc_bayes_head_any_loss(_lib.ptr(h), _lib.ptr(W), _lib.ptr(b), _lib.ptr(target), int(target.dtype == torch.int64),
+                                               _lib.ptr(class_weight), M, D, head.ng, head.np_, head.ns, f(head.T1), f(head.T2),
+                                               f(head.T3), _lib.ptr(norm), _lib.ptr(dz), _lib.ptr(part), _lib.ptr(loss),
+                                               _lib.stream_ptr()), "sgc_bayes_head_any_loss")
+        if need:
+            ctx.save_for_backward(h, dz, W)
+        ctx.head = head
+        return loss
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        h, dz, W = ctx.saved_tensors
+        head = ctx.head
+        need_h, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:9])
+        M, D = h.shape
+        lib = _lib.load()
+        g = g.to(torch.float32).contiguous()
+        dh = torch.empty_like(h) if need_h else None
+        n_part = (M + HEAD_ANY_ROWS - 1) // HEAD_ANY_ROWS
+        part = torch.empty(n_part, 64, D + 1, dtype=torch.float32, device=h.device) if need_w else None
+        _lib.check(lib.sgc_bayes_head_any_loss_bwd(_lib.ptr(h), _lib.ptr(W), _lib.ptr(dz), _lib.ptr(g), M, D, _lib.ptr(dh), _lib.ptr(part),
+                                                   _lib.stream_ptr()), "sgc_bayes_head_any_loss_bwd")
+        grads = [None] * 8
+        if need_w:
+            dwb = torch.empty(64, D + 1, dtype=torch.float32, device=h.device)
+            _lib.check(lib.sgc_bayes_head_any_wreduce(_lib.ptr(part), n_part, D, _lib.ptr(dwb), _lib.stream_ptr()),
+                       "sgc_bayes_head_any_wreduce")
+            _split_head_grads(ctx, head, dwb, D, grads)
+        return (dh, *grads, None, None, None)
 
 
 class BayesianHead(nn.Module):
@@ -647,3 +702,47 @@ class BayesianHead(nn.Module):
                 rel, sup = _head_any_forward(self, x, *self._packed(h.device))
         ng, npos = self.ng, self.np_
         return rel[:, :ng], rel[:, ng:ng + npos], rel[:, ng + npos:], sup
+
+    def _features(self, h, what):
+        if h.device.type != "cuda":
+            raise RuntimeError("BayesianHead.%s runs only on a GPU through its HIP kernels (no CPU fallback)" % what)
+        if h.dim() != 2 or h.shape[1] != self.fc5.in_features:
+            raise ValueError("h must be [M, %d], got %s" % (self.fc5.in_features, tuple(h.shape)))
+        return h.to(torch.float32).contiguous()     # autograd hands the gradient back to h in h's own dtype
+
+    def hierarchical_nll(self, h, target, class_weight=None):
+        """The reference's class-weighted hierarchical loss (``train_utils.py:116-157`` with the criteria of ``train_test.py:105-117``)
+        of this head on features ``h [M, input_dim]``, as one autograd node and without a host synchronisation: NLL of the super
+        category over the connected rows plus, per super category that has rows, the class-weighted NLL of its block.
+        ``target [M]`` int64 / int32 in ``[0, R)``; a negative value (or one past ``R``) means "no relation" and skips the row.
+        ``class_weight [R]`` positive, or None for ones.  With no connected row the loss is exactly 0 and all gradients are zero."""
+        x = self._features(h, "hierarchical_nll")
+        R = self.ng + self.np_ + self.ns
+        if not torch.is_tensor(target) or target.dtype not in (torch.int64, torch.int32) or target.shape != (x.shape[0],):
+            raise ValueError("target must be an int64 / int32 tensor of shape [M]")
+        target = target.to(x.device).contiguous()
+        if class_weight is not None:
+            class_weight = torch.as_tensor(class_weight).detach().to(x.device, torch.float32).contiguous()
+            if class_weight.shape != (R,):
+                raise ValueError("class_weight must be [%d], got %s" % (R, tuple(class_weight.shape)))
+        with torch.cuda.device(x.device):
+            return _BayesHeadLossFunction.apply(x, *self._params(), self, target, class_weight)
+
+    @torch.no_grad()
+    def candidates(self, h):
+        """``(cand_conf [M,3] f32, cand_pred [M,3] int32, sup [M,3] f32)``: per row and super category the maximum log-prob of the
+        block and its first arg-max plus the block offset (``evaluator.py:160-174``) - the layout ``Evaluator.accumulate_candidates``
+        takes; ``Evaluator_Top3.accumulate_candidates`` takes ``cand_conf.max(1)`` and ``cand_pred`` (``evaluator.py:646-648``).
+        ``cand_conf`` is bit for bit the block maxima of ``forward()``'s outputs.  No autograd."""
+        x = self._features(h, "candidates")
+        M, D = x.shape
+        W, b = self._packed(x.device)
+        conf = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+        pred = torch.empty(M, 3, dtype=torch.int32, device=x.device)
+        sup = torch.empty(M, 3, dtype=torch.float32, device=x.device)
+        f = ctypes.c_float
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.load().sgc_bayes_head_any_candidates(_lib.ptr(x), _lib.ptr(W), _lib.ptr(b), M, D, self.ng, self.np_, self.ns,
+                                                                 f(self.T1), f(self.T2), f(self.T3), _lib.ptr(conf), _lib.ptr(pred),
+                                                                 _lib.ptr(sup), _lib.stream_ptr()), "sgc_bayes_head_any_candidates")
+        return conf, pred, sup
