@@ -282,6 +282,32 @@ int sgc_fc1_xrows(const void* dh1, const int* gather, const int* dest, int n_ent
 int sgc_fc1_windows_dgrad(const void* gwm, const void* w1pT, const int* tile_group, void* dywm, int rows, void* stream);
 int sgc_fc1_windows_wgrad(const void* gwm, const void* ywm_bf16, const int* goff, float* dw, int rows, void* stream);
 
+/* COMPACT window-major row space of the second level (csrc/kernels_shared.hip, "fc1 over shared windows"): outside R_o a pseudo-pair's
+ * value IS the background row of its image, so group w = [n_img background rows (row goff[w] + image)][the pseudo-pairs ps with w inside
+ * R_o, in ps order][X entries][zero rows up to a multiple of 256].  goff / gend / tile_group / dest keep their meaning; the GEMM entries
+ * above run on it unchanged (sgc_fc1_windows_gemm_x16: pass the groups' first X rows as ``goff`` and n_pseudo = 0; the background maps'
+ * conv3 is sgc_conv3_relu_pool_wm with n_pairs = n_img).
+ *   sgc_window_rows_compact             prow [2*n_obj*64]: prow[ps*64 + w] = the row holding pseudo-pair ps's value at window w (its own
+ *                                       row, or the background row of its image)
+ *   sgc_window_rows_objects_compact     sgc_window_rows_objects through prow
+ *   sgc_shared_objects_fill_argmax      the routing-code half of sgc_shared_objects_fill_rows (pair-major, no y rows)
+ *   sgc_fc1_integral_rows               sgc_fc1_integral reading row prow[ps*64 + w]: the same values in the same order, same bits
+ *   sgc_fc1_gsum_groups                 number of [64][4096] f32 blocks of ``part`` for n_obj objects in n_img images
+ *   sgc_fc1_gsum_compact                sgc_fc1_gsum writing a pseudo-pair's rows only inside R_o; the background row (b, w) of gwm = the f32
+ *                                       sum, in subject order, over the subjects i of image b with w outside R_i of the sum sgc_fc1_gsum
+ *                                       forms for (0, i, w), rounded to bf16 once (no atomics; the same bits on every run)
+ *   sgc_shared_objects_bg_grad_compact  dy_bg [n_img*64][1024] = the background rows of dywm */
+int sgc_window_rows_compact(const int* bbox, const int* obj_img, int n_obj, int n_img, const int* goff, int* prow, void* stream);
+int sgc_window_rows_objects_compact(const int* codes, int n, const int* prow, int n_pairs, int* dest, void* stream);
+int sgc_shared_objects_fill_argmax(const int* bbox, const int* obj_img, int n_obj, const unsigned char* argmax_bg, unsigned char* argmax_ps,
+                                   void* stream);
+int sgc_fc1_integral_rows(const float* owm, const int* prow, int n_pseudo, float* S, void* stream);
+int sgc_fc1_gsum_groups(int n_obj, int n_img);
+int sgc_fc1_gsum_compact(const void* dh1, const int* bbox, const int* sub_idx, const int* obj_idx, const int* sub_ptr, const int* sub_list,
+                         const int* obj_ptr, const int* obj_list, const int* img_ptr, int n_img, const int* goff, const int* prow, int n_obj,
+                         void* gwm, float* part, void* stream);
+int sgc_shared_objects_bg_grad_compact(int n_img, const int* goff, const void* dywm, void* dy_bg, void* stream);
+
 /* h1 [n_pairs][4096] f16 = dropout(relu(y[n_pairs][K] * w1p[4096][K]^T + b))   (model.py:148-149; columns of w1p in (window, channel) order) */
 int sgc_fc1_relu(const void* y, const void* w1p, const float* b, void* h1, int n_pairs, int K, int drop_enable, unsigned drop_seed, void* stream);
 

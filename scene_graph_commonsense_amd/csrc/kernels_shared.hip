@@ -100,9 +100,11 @@ __global__ __launch_bounds__(256) void shared_fill_object_rows_kernel(const int*
         const int ps = (int)(row >> 6), w = (int)(row & 63);
         const int o = ps >= n_obj ? ps - n_obj : ps;
         if (in_rect(object_windows(bbox + 4 * o), w & 7, w >> 3)) continue;         // computed for the object (window-list entry)
-        const long src = (long)obj_img[o] * 64 + w, dst = (long)goff[w] + ps;
-        ywm[dst * 128 + lane] = y_bg[src * 128 + lane];
-        ywm[dst * 128 + 64 + lane] = y_bg[src * 128 + 64 + lane];
+        const long src = (long)obj_img[o] * 64 + w, dst = ywm ? (long)goff[w] + ps : 0;
+        if (ywm) {
+            ywm[dst * 128 + lane] = y_bg[src * 128 + lane];
+            ywm[dst * 128 + 64 + lane] = y_bg[src * 128 + 64 + lane];
+        }
         if (ywm_bf) {
             ywm_bf[dst * 128 + lane] = ybf_bg[src * 128 + lane];
             ywm_bf[dst * 128 + 64 + lane] = ybf_bg[src * 128 + 64 + lane];
@@ -158,6 +160,47 @@ __global__ __launch_bounds__(256) void shared_bg_grad_kernel(const int* __restri
 #pragma unroll
         for (int k = 0; k < 8; ++k) oah[k] = f32_to_bf16_bits(acc[k]);
         *reinterpret_cast<uint4*>(dy_bg + bw * 1024 + half * 512 + lane * 8) = oa;
+    }
+}
+
+// ---- compact window-major row space (second level; see "fc1 over shared windows"): a background copy is never a row.
+// prow[ps*64 + w] = the row that holds pseudo-pair ps's value at window w: its own row goff[w] + n_img + (number of pseudo-pairs
+// ps' < ps with w inside R_o') when w is inside R_o, else the background row goff[w] + image(o).  One workgroup per window.
+__global__ __launch_bounds__(256) void compact_rows_kernel(const int* __restrict__ bbox, const int* __restrict__ obj_img, int n_obj, int n_img,
+                                                           const int* __restrict__ goff, int* __restrict__ prow) {
+    __shared__ int s_wave[4];
+    const int w = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int g0 = goff[w];
+    int base = g0 + n_img;
+    for (int ps0 = 0; ps0 < 2 * n_obj; ps0 += 256) {
+        const int ps = ps0 + threadIdx.x;
+        const bool live = ps < 2 * n_obj;
+        const int o = live ? (ps >= n_obj ? ps - n_obj : ps) : 0;
+        const bool in = live && in_rect(object_windows(bbox + 4 * o), w & 7, w >> 3);
+        const unsigned long long m = __ballot(in);
+        if (lane == 0) s_wave[wid] = __popcll(m);
+        __syncthreads();
+        int before = base;
+        for (int k = 0; k < wid; ++k) before += s_wave[k];
+        before += __popcll(m & ((1ull << lane) - 1ull));
+        if (live) prow[ps * 64 + w] = in ? before : g0 + obj_img[o];
+        base += s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+        __syncthreads();
+    }
+}
+// rows of the pseudo-pairs' own windows (entries of the window list behind the real pairs'): dest[i] = prow[code - 64 P]
+__global__ void compact_rows_objects_kernel(const int* __restrict__ codes, int n, const int* __restrict__ prow, int P, int* __restrict__ dest) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dest[i] = prow[codes[i] - 64 * P];
+}
+// gradient of the background maps in the compact row space: the background rows of dywm, brought to map order
+__global__ __launch_bounds__(256) void compact_bg_grad_kernel(const int* __restrict__ goff, const uint4* __restrict__ dywm, uint4* __restrict__ dy_bg,
+                                                              long n_rows) {
+    const int lane = threadIdx.x & 63;
+    for (long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6); row < n_rows; row += (long)gridDim.x * 4) {
+        const long src = (long)goff[row & 63] + (row >> 6);
+        dy_bg[row * 128 + lane] = dywm[src * 128 + lane];
+        dy_bg[row * 128 + 64 + lane] = dywm[src * 128 + 64 + lane];
     }
 }
 
@@ -665,15 +708,23 @@ __global__ __launch_bounds__(256) void pair_contract_windows_kernel(const u16* _
 //   S_o  = 2-D inclusive prefix sums of T_o over the 8x8 window grid (9x9 with a zero border)
 //   h_pre[p] = b + S_i[all] - S_i[R_j] + S'_j[R_j] - S'_j[X_p] + sum_{e in X_p} O[dest[e]]          (rectangle sums = 4 look-ups)
 // which is the same sum in a different order (f32 round-off instead of bit equality with the [P, 65536] GEMM).
+// COMPACT form of the row space (second level, Tuning.compact_object_rows): outside R_o a pseudo-pair's y row is the background row of
+// its image, so it is not a row of its own: group w = [the n_img background rows of window w: row goff[w] + image][the pseudo-pairs
+// (role, o) with w inside R_o, ps order][X entries][zero rows], and prow[ps*64 + w] (compact_rows_kernel) is the row that holds the
+// pseudo-pair's value at window w - its own or the background's.  T_o[w] is read through prow (same values, same order of additions:
+// the same S, own sums and h1, bit for bit); role-1 rows outside R_o only ever carried zero gradients; the gradient rows of the role-0
+// copies are summed per (image, window) in f32 before they are rounded (fc1_gsum_compact_kernel).  On the benchmark's boxes 68.8 % of the
+// 65 536 pseudo rows were such copies: 14.6 % of the rows of all three fc1 GEMMs (profiles/r07_compact_rows_ab.txt).
 // Row pitch of the f32 products owm in floats: 4096 + 256 B.  With the power-of-two pitch every row of a 256 x 256 output tile starts
 // 16 KiB after the previous one and the tile's stores drain 10 % slower (tools/fc1_windows_microbench.py: 3.18 -> 2.86 ms per launch
 // with 16-byte stores; profiles/r03_fc1_windows_microbench*.txt).
 static inline int owm_pitch() { return sgc_tuning().owm_pitch; }     // 4160
+// ``prow`` (compact row space): the row of (ps, window) is prow[ps*64 + window] instead of goff[window] + ps
 __global__ __launch_bounds__(256) void fc1_integral_kernel(const float* __restrict__ owm, int pitch, const int* __restrict__ goff, int n2,
-                                                           float* __restrict__ S) {
-    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-    const int c = (int)(idx & 4095);
-    const int ps = (int)(idx >> 12);
+                                                           float* __restrict__ S, const int* __restrict__ prow) {
+    // 16 workgroups per pseudo-pair: ps is uniform over the workgroup, so the 64 row look-ups are scalar loads ahead of the sums
+    const int c = (int)(blockIdx.x & 15) * 256 + threadIdx.x;
+    const int ps = (int)(blockIdx.x >> 4);
     if (ps >= n2) return;
     float* So = S + (long)ps * 81 * 4096 + c;
     float col[8];
@@ -686,7 +737,8 @@ __global__ __launch_bounds__(256) void fc1_integral_kernel(const float* __restri
         So[(long)((y + 1) * 9) * 4096] = 0.f;
 #pragma unroll
         for (int x = 0; x < 8; ++x) {
-            run += owm[((long)goff[y * 8 + x] + ps) * pitch + c];
+            const long row = prow ? (long)prow[ps * 64 + y * 8 + x] : (long)goff[y * 8 + x] + ps;
+            run += owm[row * pitch + c];
             col[x] += run;
             So[(long)((y + 1) * 9 + x + 1) * 4096] = col[x];
         }
@@ -871,6 +923,141 @@ __global__ __launch_bounds__(256) void fc1_gsum_kernel(const u16* __restrict__ d
                 gwm[((long)goff[w] + ps) * 4096 + c] = f32_to_bf16_bits(acc[j][r]);
             }
     }
+}
+
+// ---- the same sums for the COMPACT row space (rows through ``prow``): a pseudo-pair has a row only at the windows of R_o.
+//   role 1: the mask is own & ~pm, so nothing exists outside R_o - the workgroup of fc1_gsum_kernel, writing |R_o| rows.
+//   role 0: outside R_i the copy was the image's background row (b, w), whose gradient is the sum over the subjects i of image b
+//           with w outside R_i of what is accumulated for (0, i, w).  A workgroup takes GSUM_GRP consecutive subjects of ONE image
+//           and 128 channels (a wave per 32-channel tile): per subject the f32 accumulators of the windows inside R_i leave as that
+//           subject's bf16 rows, the others are added - in subject order - to a second set of f32 accumulators, which leaves as the
+//           group's partial sums part[group][64][4096] f32.  fc1_gsum_bg_kernel adds an image's groups in group order and rounds
+//           once.  No atomics: the order is fixed.  Groups are numbered image after image, ceil(n_b / GSUM_GRP) per image; the host
+//           launches an upper bound (sgc_fc1_gsum_groups) and the workgroups behind the last group leave.
+constexpr int GSUM_GRP = 8;
+__device__ __forceinline__ unsigned long long rect_mask(const WRect& r) {
+    unsigned long long m = 0ull;
+    for (int y = r.y0; y < r.y1; ++y) m |= (((1ull << r.x1) - (1ull << r.x0)) & 0xffull) << (8 * y);
+    return m;
+}
+// image and first subject of role-0 group t; false when t is behind the last group
+__device__ __forceinline__ bool gsum_group(const int* __restrict__ img_ptr, int n_img, int t, int& b, int& o0, int& o1) {
+    int g = 0;
+    for (b = 0; b < n_img; ++b) {
+        const int n = img_ptr[b + 1] - img_ptr[b], ng = (n + GSUM_GRP - 1) / GSUM_GRP;
+        if (t < g + ng) {
+            o0 = img_ptr[b] + (t - g) * GSUM_GRP;
+            o1 = min(o0 + GSUM_GRP, img_ptr[b + 1]);
+            return true;
+        }
+        g += ng;
+    }
+    return false;
+}
+__global__ __launch_bounds__(256) void fc1_gsum_compact_kernel(const u16* __restrict__ dh, const int* __restrict__ bbox, const int* __restrict__ sub,
+                                                               const int* __restrict__ obj, const int* __restrict__ sub_ptr,
+                                                               const int* __restrict__ sub_list, const int* __restrict__ obj_ptr,
+                                                               const int* __restrict__ obj_list, const int* __restrict__ img_ptr, int n_img,
+                                                               const int* __restrict__ prow, int n_obj, int n_grp, u16* __restrict__ gwm,
+                                                               float* __restrict__ part) {
+    __shared__ int s_pair[GSUM_MAXP];
+    __shared__ unsigned long long s_mask[GSUM_MAXP];
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int l31 = lane & 31, kh = lane >> 5;
+    const int role = (int)blockIdx.x >= n_grp * 32 ? 1 : 0;
+    int o0, o1, n_tiles, c_base, grp = 0;
+    if (role) {
+        const int k = (int)blockIdx.x - n_grp * 32;
+        o0 = k >> 2; o1 = o0 + 1; n_tiles = 8; c_base = (k & 3) * 1024 + wid * 256;
+    } else {
+        int b;
+        grp = (int)blockIdx.x >> 5;
+        if (!gsum_group(img_ptr, n_img, grp, b, o0, o1)) return;
+        n_tiles = 1; c_base = ((int)blockIdx.x & 31) * 128 + wid * 32;
+    }
+    const int* ptr = role ? obj_ptr : sub_ptr;
+    const int* list = role ? obj_list : sub_list;
+    f32x16 bg[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) bg[j][r] = 0.f;
+    for (int o = o0; o < o1; ++o) {
+        const int i0 = ptr[o], i1 = ptr[o + 1];
+        const unsigned long long own = rect_mask(object_windows(bbox + 4 * o));
+        const int* pr = prow + ((long)role * n_obj + o) * 64;
+        for (int tile = 0; tile < n_tiles; ++tile) {
+            const int c = c_base + tile * 32 + l31;
+            f32x16 acc[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+            for (int base = i0; base < i1; base += GSUM_MAXP) {
+                const int n = min(GSUM_MAXP, i1 - base);
+                if (tile == 0 || i1 - i0 > GSUM_MAXP) {          // staged once per object unless it has more than 512 partners
+                    __syncthreads();
+                    for (int k = threadIdx.x; k < n; k += 256) {
+                        const int p = list[base + k];
+                        const unsigned long long pm = rect_mask(object_windows(bbox + 4 * (role ? sub[p] : obj[p])));
+                        s_pair[k] = p;
+                        s_mask[k] = role ? (own & ~pm) : ~pm;
+                    }
+                    __syncthreads();
+                }
+                for (int k0 = 0; k0 < n; k0 += 16) {
+                    s16x8 bfr, af0, af1;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) {
+                        const int k = k0 + 8 * kh + j;
+                        const bool ok = k < n;
+                        const unsigned long long m = ok ? s_mask[k] : 0ull;
+                        bfr[j] = ok ? (short)dh[(long)s_pair[k] * 4096 + c] : (short)0;
+                        af0[j] = ((m >> l31) & 1ull) ? (short)0x3F80 : (short)0;
+                        af1[j] = ((m >> (32 + l31)) & 1ull) ? (short)0x3F80 : (short)0;
+                    }
+                    acc[0] = mfma32<ELEM_BF16>(af0, bfr, acc[0]);
+                    acc[1] = mfma32<ELEM_BF16>(af1, bfr, acc[1]);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int w = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    if ((own >> w) & 1ull) gwm[(long)pr[w] * 4096 + c] = f32_to_bf16_bits(acc[j][r]);
+                    else bg[j][r] += acc[j][r];               // role 1: zero (the mask is inside ``own``), never stored
+                }
+        }
+    }
+    if (role) return;
+    const int c = c_base + l31;
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int w = j * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            part[((long)grp * 64 + w) * 4096 + c] = bg[j][r];
+        }
+}
+// gwm[goff[w] + b] = bf16(the sum of the partial sums of image b's groups, in group order); one thread per (image, window, 4 channels)
+__global__ __launch_bounds__(256) void fc1_gsum_bg_kernel(const float* __restrict__ part, const int* __restrict__ img_ptr, int n_img,
+                                                          const int* __restrict__ goff, u16* __restrict__ gwm) {
+    const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+    const int c = (int)(idx & 1023) * 4, w = (int)((idx >> 10) & 63), b = (int)(idx >> 16);
+    if (b >= n_img) return;
+    int g0 = 0;
+    for (int k = 0; k < b; ++k) g0 += (img_ptr[k + 1] - img_ptr[k] + GSUM_GRP - 1) / GSUM_GRP;
+    const int g1 = g0 + (img_ptr[b + 1] - img_ptr[b] + GSUM_GRP - 1) / GSUM_GRP;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int g = g0; g < g1; ++g) {
+        const float4 t = *reinterpret_cast<const float4*>(part + ((long)g * 64 + w) * 4096 + c);
+        a.x += t.x; a.y += t.y; a.z += t.z; a.w += t.w;
+    }
+    uint2 o;
+    o.x = (unsigned)f32_to_bf16_bits(a.x) | ((unsigned)f32_to_bf16_bits(a.y) << 16);
+    o.y = (unsigned)f32_to_bf16_bits(a.z) | ((unsigned)f32_to_bf16_bits(a.w) << 16);
+    *reinterpret_cast<uint2*>(gwm + ((long)goff[w] + b) * 4096 + c) = o;
 }
 
 // X rows of the window-major gradient: gwm[dest[e]] = dh1[pair of entry e]; and the padding rows of every group are zeroed in gwm
@@ -1567,7 +1754,7 @@ int sgc_fc1_windows_gemm_x16(const void* ywm, const void* w1p, const int* tile_g
 int sgc_fc1_integral(const float* owm, const int* goff, int n_pseudo, float* S, void* stream) {
     if (n_pseudo <= 0) return SGC_OK;
     SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, owm_pitch(), goff,
-               n_pseudo, S);
+               n_pseudo, S, (const int*)nullptr);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }
@@ -1804,6 +1991,66 @@ int sgc_windows_wgrad_gather(const void* dy3x, const void* z_pad_bf16, const int
     p.lda = 1024; p.ldc = 9 * 512; p.slab_stride = 1024L * 9 * 512; p.lgS = 4; p.Cin = 512; p.gather = gather;
     if (splits <= 0) splits = tn_auto_splits(4 * 18, rows >> 6);
     return launch_gemm_tn_pp<ELEM_BF16, BMODE_GATHER, 0>(p, splits, n_slabs, (hipStream_t)stream);
+}
+
+
+// ---- compact window-major row space (``Tuning.compact_object_rows``): group w = [n_img background rows][the pseudo-pairs with w inside
+// R_o, ps order][X entries][zero rows to a multiple of 256]; goff / gend / tile_group / dest keep their meaning
+int sgc_window_rows_compact(const int* bbox, const int* obj_img, int n_obj, int n_img, const int* goff, int* prow, void* stream) {
+    if (n_obj <= 0) return SGC_OK;
+    SGC_LAUNCH(compact_rows_kernel, dim3(64), dim3(256), 0, (hipStream_t)stream, bbox, obj_img, n_obj, n_img, goff, prow);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+int sgc_window_rows_objects_compact(const int* codes, int n, const int* prow, int n_pairs, int* dest, void* stream) {
+    if (n <= 0) return SGC_OK;
+    SGC_LAUNCH(compact_rows_objects_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, codes, n, prow, n_pairs, dest);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+// the pair-major routing rows of the pseudo-pairs outside R_o (copies of the background map's), without any y row
+int sgc_shared_objects_fill_argmax(const int* bbox, const int* obj_img, int n_obj, const unsigned char* argmax_bg, unsigned char* argmax_ps,
+                                   void* stream) {
+    if (n_obj <= 0) return SGC_OK;
+    if (!argmax_bg || !argmax_ps) return SGC_ERR_ARG;
+    const long rows = 2L * n_obj * 64;
+    SGC_LAUNCH(shared_fill_object_rows_kernel, dim3(grid_cap(rows, 4, 131072)), dim3(256), 0, (hipStream_t)stream, bbox, obj_img, n_obj,
+               (const int*)nullptr, (const uint4*)nullptr, (const uint4*)nullptr, (const uint4*)argmax_bg, (uint4*)nullptr, (uint4*)nullptr,
+               (uint4*)argmax_ps, rows);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+int sgc_fc1_integral_rows(const float* owm, const int* prow, int n_pseudo, float* S, void* stream) {
+    if (n_pseudo <= 0) return SGC_OK;
+    if (!prow) return SGC_ERR_ARG;
+    SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, owm_pitch(),
+               (const int*)nullptr, n_pseudo, S, prow);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+// upper bound of the number of role-0 groups (sum over the images of ceil(n_b / 8)) known from the totals alone: sizes ``part``
+int sgc_fc1_gsum_groups(int n_obj, int n_img) { return (n_obj + GSUM_GRP - 1) / GSUM_GRP + n_img; }
+// part: [sgc_fc1_gsum_groups][64][4096] f32 scratch
+int sgc_fc1_gsum_compact(const void* dh1, const int* bbox, const int* sub_idx, const int* obj_idx, const int* sub_ptr, const int* sub_list,
+                         const int* obj_ptr, const int* obj_list, const int* img_ptr, int n_img, const int* goff, const int* prow, int n_obj,
+                         void* gwm, float* part, void* stream) {
+    if (n_obj <= 0 || n_img <= 0) return SGC_OK;
+    const int n_grp = sgc_fc1_gsum_groups(n_obj, n_img);
+    SGC_LAUNCH(fc1_gsum_compact_kernel, dim3((unsigned)(n_grp * 32 + n_obj * 4)), dim3(256), 0, (hipStream_t)stream, (const u16*)dh1, bbox, sub_idx,
+               obj_idx, sub_ptr, sub_list, obj_ptr, obj_list, img_ptr, n_img, prow, n_obj, n_grp, (u16*)gwm, part);
+    SGC_CHECK_LAUNCH();
+    SGC_LAUNCH(fc1_gsum_bg_kernel, dim3((unsigned)(n_img * 256)), dim3(256), 0, (hipStream_t)stream, (const float*)part, img_ptr, n_img, goff,
+               (u16*)gwm);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+int sgc_shared_objects_bg_grad_compact(int n_img, const int* goff, const void* dywm, void* dy_bg, void* stream) {
+    if (n_img <= 0) return SGC_OK;
+    const long rows = (long)n_img * 64;
+    SGC_LAUNCH(compact_bg_grad_kernel, dim3(grid_cap(rows, 4, 65536)), dim3(256), 0, (hipStream_t)stream, goff, (const uint4*)dywm, (uint4*)dy_bg,
+               rows);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
 }
 
 }  // extern "C"

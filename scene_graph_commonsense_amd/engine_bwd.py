@@ -140,7 +140,7 @@ class BackwardMixin:
 
         # ---- fc1
         if getattr(ctx, "shared", None) is not None and ctx.shared.get("wm") is not None:
-            dy = self._fc1_backward_rows(ctx, dh1, sub_csr, obj_csr, side, grads, grad_hook)
+            dy = self._fc1_backward_rows(ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook)
         else:
             dy = self._fc1_backward_pairs(ctx, dh1, side, grads, grad_hook)
 
@@ -260,16 +260,24 @@ class BackwardMixin:
         self._timed("fc1_dgrad", lambda: _lib.check(lib.sgc_fc1_dgrad(_lib.ptr(dh1), _lib.ptr(w1pT), _lib.ptr(dy), P, 65536, st()), "sgc_fc1_dgrad"))
         return dy
 
-    def _fc1_backward_rows(self, ctx, dh1, sub_csr, obj_csr, side, grads, grad_hook):
+    def _fc1_backward_rows(self, ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook):
         """fc1 backward over the window-major rows (``csrc/kernels_shared.hip``): per-object sums of dh1 + one copy of dh1 per X entry,
         then the grouped weight- and data-gradient GEMMs; returns dywm [rows, 1024] (window-major pooled gradient)."""
         lib, w, ws, st, sh = self.lib, self.w, self.scratch, self._st, ctx.shared
         wm = sh["wm"]
         gwm = ws.get("gwm", wm["rows"] * 4096, torch.bfloat16)
+        if wm["prow"] is not None:       # compact row space: rows only inside R_o, the background rows collect the rest (f32 partial sums)
+            part = ws.get("gsum_part", int(lib.sgc_fc1_gsum_groups(ctx.n_obj, ctx.n_img)) * 64 * 4096, torch.float32)
+            gsum = lambda: _lib.check(lib.sgc_fc1_gsum_compact(
+                _lib.ptr(dh1), _lib.ptr(ctx.bbox), _lib.ptr(ctx.sub_idx), _lib.ptr(ctx.obj_idx), _lib.ptr(sub_csr[0]), _lib.ptr(sub_csr[1]),
+                _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(img_ptr), ctx.n_img, _lib.ptr(wm["goff"]), _lib.ptr(wm["prow"]), ctx.n_obj,
+                _lib.ptr(gwm), _lib.ptr(part), st()), "sgc_fc1_gsum_compact")
+        else:
+            gsum = lambda: _lib.check(lib.sgc_fc1_gsum(
+                _lib.ptr(dh1), _lib.ptr(ctx.bbox), _lib.ptr(ctx.sub_idx), _lib.ptr(ctx.obj_idx), _lib.ptr(sub_csr[0]), _lib.ptr(sub_csr[1]),
+                _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(wm["goff"]), ctx.n_obj, _lib.ptr(gwm), st()), "sgc_fc1_gsum")
         self._timed("fc1_bwd_rows", lambda: (
-            _lib.check(lib.sgc_fc1_gsum(_lib.ptr(dh1), _lib.ptr(ctx.bbox), _lib.ptr(ctx.sub_idx), _lib.ptr(ctx.obj_idx), _lib.ptr(sub_csr[0]),
-                                        _lib.ptr(sub_csr[1]), _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(wm["goff"]), ctx.n_obj,
-                                        _lib.ptr(gwm), st()), "sgc_fc1_gsum"),
+            gsum(),
             _lib.check(lib.sgc_fc1_xrows(_lib.ptr(dh1), _lib.ptr(sh.get("gather_all", sh["gather"])), _lib.ptr(wm["dest"]), wm["E"], _lib.ptr(wm["goff"]),
                                          _lib.ptr(wm["gend"]), _lib.ptr(gwm), _lib.ptr(sh["ywm_bf"]), st()), "sgc_fc1_xrows")))
         dy = ws.get("dywm", wm["rows"] * 1024, torch.bfloat16)
@@ -351,8 +359,12 @@ class BackwardMixin:
         if objects:
             n_maps, map0 = n_img, P + n2
             dy_maps = ws.get("dy_bg", n_img * 65536, torch.bfloat16)
-            _lib.check(lib.sgc_shared_objects_bg_grad(_lib.ptr(ctx.bbox), _lib.ptr(img_ptr), n_obj, n_img, _lib.ptr(wm["goff"]), _lib.ptr(dy),
-                                                      _lib.ptr(dy_maps), st()), "sgc_shared_objects_bg_grad")
+            if wm["prow"] is not None:       # compact row space: the background rows of dywm are the maps' gradient
+                _lib.check(lib.sgc_shared_objects_bg_grad_compact(n_img, _lib.ptr(wm["goff"]), _lib.ptr(dy), _lib.ptr(dy_maps), st()),
+                           "sgc_shared_objects_bg_grad_compact")
+            else:
+                _lib.check(lib.sgc_shared_objects_bg_grad(_lib.ptr(ctx.bbox), _lib.ptr(img_ptr), n_obj, n_img, _lib.ptr(wm["goff"]), _lib.ptr(dy),
+                                                          _lib.ptr(dy_maps), st()), "sgc_shared_objects_bg_grad")
             am_maps = sh["am_bg"]
         else:
             n_maps, map0 = n2, P

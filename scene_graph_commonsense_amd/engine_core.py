@@ -166,6 +166,9 @@ class Tuning:
     shared_conv3: bool = True
     shared_fc1: bool = True
     shared_objects: bool = True
+    compact_object_rows: bool = True  # second level + shared fc1: a pseudo-pair has window-major rows only inside R_o, elsewhere fc1 and its backward
+                                      # use the image's background row (off: every pseudo-pair has 64 rows, two thirds of them copies; same forward
+                                      # bits, the background rows' gradient summed before the product instead of after it)
     shared_bwd: bool = True
     shared_max_fraction: float = 0.5
     bwd_streams: bool = True

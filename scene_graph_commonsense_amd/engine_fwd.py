@@ -99,14 +99,18 @@ class ForwardMixin:
         if TUNING.fc1_x16:
             oxh = sc.get("oxh", wm["rows"] * 4096, torch.float16)
             self._timed("fc1_fwd_windows", lambda: _lib.check(lib.sgc_fc1_windows_gemm_x16(
-                _lib.ptr(ywm), _lib.ptr(w1p), _lib.ptr(wm["tile_group"]), _lib.ptr(wm["goff"]), wm["n2"], _lib.ptr(owm), _lib.ptr(oxh), wm["rows"],
+                _lib.ptr(ywm), _lib.ptr(w1p), _lib.ptr(wm["tile_group"]), _lib.ptr(wm["x_tab"]), wm["x_first"], _lib.ptr(owm), _lib.ptr(oxh), wm["rows"],
                 self._st()), "sgc_fc1_windows_gemm_x16"))
         else:
             self._timed("fc1_fwd_windows", lambda: _lib.check(lib.sgc_fc1_windows_gemm(
                 _lib.ptr(ywm), _lib.ptr(w1p), _lib.ptr(wm["tile_group"]), _lib.ptr(owm), wm["rows"], self._st()), "sgc_fc1_windows_gemm"))
         S = sc.get("fc1_S", wm["n2"] * 81 * 4096, torch.float32)
-        self._timed("fc1_fwd_integral", lambda: _lib.check(lib.sgc_fc1_integral(_lib.ptr(owm), _lib.ptr(wm["goff"]), wm["n2"], _lib.ptr(S), self._st()),
-                                                           "sgc_fc1_integral"))
+        if wm["prow"] is not None:         # compact row space: a pseudo-pair's value outside R_o is read from the background row
+            self._timed("fc1_fwd_integral", lambda: _lib.check(lib.sgc_fc1_integral_rows(_lib.ptr(owm), _lib.ptr(wm["prow"]), wm["n2"], _lib.ptr(S),
+                                                                                         self._st()), "sgc_fc1_integral_rows"))
+        else:
+            self._timed("fc1_fwd_integral", lambda: _lib.check(lib.sgc_fc1_integral(_lib.ptr(owm), _lib.ptr(wm["goff"]), wm["n2"], _lib.ptr(S), self._st()),
+                                                               "sgc_fc1_integral"))
         own = None
         if TUNING.fc1_own_sums:            # S'_j[R_j] per object: read once per pair instead of four corners
             own = sc.get("fc1_own", max(n_obj, 1) * 4096, torch.float32)
@@ -167,15 +171,25 @@ class ForwardMixin:
             if objects:
                 # second level: the pseudo-pairs' windows R_o are entries of the window list; the other rows are the background maps'
                 zb = zt[n2 * 18 * 18 * 512:]
-                y_bg = sc.get("y_bg", n_img * 65536, torch.float16)
-                ybf_bg = sc.get("ybf_bg", n_img * 65536, torch.bfloat16) if y_bf is not None else None
                 am_bg = own.get("am_bg", n_img * 65536, torch.uint8) if am is not None else None
-                self._timed("conv3_fwd_objects", lambda: _lib.check(lib.sgc_conv3_relu_pool(
-                    _lib.ptr(zb), _lib.ptr(self.w["w3r"]), _lib.ptr(self.w["b3"]), _lib.ptr(y_bg), _lib.ptr(am_bg), _lib.ptr(ybf_bg), n_img,
-                    self._st()), "sgc_conv3_relu_pool"))
-                _lib.check(lib.sgc_shared_objects_fill_rows(_lib.ptr(bbox), _lib.ptr(obj_img), n_obj, _lib.ptr(wm["goff"]), _lib.ptr(y_bg),
-                                                            _lib.ptr(ybf_bg), _lib.ptr(am_bg), _lib.ptr(y), _lib.ptr(y_bf), _lib.ptr(am_ps),
-                                                            self._st()), "sgc_shared_objects_fill_rows")
+                if wm["prow"] is not None:
+                    # compact row space: the background maps' rows ARE rows of the space (goff[w] + image), written by the epilogue;
+                    # no pseudo-pair row is a copy.  Only the pair-major routing rows are still copied.
+                    self._timed("conv3_fwd_objects", lambda: _lib.check(lib.sgc_conv3_relu_pool_wm(
+                        _lib.ptr(zb), _lib.ptr(self.w["w3r"]), _lib.ptr(self.w["b3"]), _lib.ptr(wm["goff"]), _lib.ptr(y), _lib.ptr(am_bg),
+                        _lib.ptr(y_bf), n_img, self._st()), "sgc_conv3_relu_pool_wm"))
+                    if am_ps is not None:
+                        _lib.check(lib.sgc_shared_objects_fill_argmax(_lib.ptr(bbox), _lib.ptr(obj_img), n_obj, _lib.ptr(am_bg), _lib.ptr(am_ps),
+                                                                      self._st()), "sgc_shared_objects_fill_argmax")
+                else:
+                    y_bg = sc.get("y_bg", n_img * 65536, torch.float16)
+                    ybf_bg = sc.get("ybf_bg", n_img * 65536, torch.bfloat16) if y_bf is not None else None
+                    self._timed("conv3_fwd_objects", lambda: _lib.check(lib.sgc_conv3_relu_pool(
+                        _lib.ptr(zb), _lib.ptr(self.w["w3r"]), _lib.ptr(self.w["b3"]), _lib.ptr(y_bg), _lib.ptr(am_bg), _lib.ptr(ybf_bg), n_img,
+                        self._st()), "sgc_conv3_relu_pool"))
+                    _lib.check(lib.sgc_shared_objects_fill_rows(_lib.ptr(bbox), _lib.ptr(obj_img), n_obj, _lib.ptr(wm["goff"]), _lib.ptr(y_bg),
+                                                                _lib.ptr(ybf_bg), _lib.ptr(am_bg), _lib.ptr(y), _lib.ptr(y_bf), _lib.ptr(am_ps),
+                                                                self._st()), "sgc_shared_objects_fill_rows")
                 out["am_bg"] = am_bg
             else:
                 self._timed("conv3_fwd_objects", lambda: _lib.check(lib.sgc_conv3_relu_pool_wm(
@@ -240,7 +254,7 @@ class ForwardMixin:
         z = ws.get("z_pad", Pt * 18 * 18 * 512, torch.float16)     # border stays zero: only interiors are written
         # the row plan (a sort, a dozen small launches, four blocking host-to-device copies) goes BEFORE the pair expansion: its
         # launches are then behind the host when the 1.4 ms expansion kernel starts, instead of leaving the GPU idle between them
-        wm = self.window_major_rows(plan, P, 2 * n_obj) if shared is not None and wm_mode else None
+        wm = self.window_major_rows(plan, P, 2 * n_obj, shared[0], shared[1]) if shared is not None and wm_mode else None
         self.expand(U, V, sub_idx, obj_idx, P, z, dense=dense, pixrect=None if plan is None else plan["pixrect"])
         am = ws.get("argmax", Pt * 65536, torch.uint8) if keep_argmax else None
         h1 = ws.get("h1", Ppad * 4096, torch.float16)
@@ -408,7 +422,7 @@ class ForwardMixin:
         ctx.z_bf_base = P if (narrow and TUNING.patch_wgrad and dense is not None and 0 < dense[2] <= 150) else 0
         z_bf = ws.get("z_pad_bf", (Pt - ctx.z_bf_base) * 18 * 18 * 512, torch.bfloat16)
         amz = ws.get("amz", Pt * 256 * 256, torch.uint8)             # two 4-bit routing codes per byte
-        wm = self.window_major_rows(plan, P, 2 * ctx.n_obj) if wm_mode else None     # before the expansion: see forward_pairs
+        wm = self.window_major_rows(plan, P, 2 * ctx.n_obj, bbox, obj_img) if wm_mode else None     # before the expansion: see forward_pairs
         self.expand(ctx.uv[0], ctx.uv[1], sub_idx, obj_idx, P, z, None if ctx.z_bf_base else z_bf, amz, dense=dense,
                     pixrect=plan["pixrect"] if narrow else None)
         ctx.z_bf = z_bf

@@ -53,7 +53,7 @@ class PlanMixin:
         self._xw_linear = None
         return dict(gather=gather, incl=incl, n_total=incl[Pt - 1:], pixrect=pixrect, bound=total, entries=total if exact else None,
                     entries_real=e_real if exact else None, window_entries=hint.get("per_window"), objects=objects, P=P, n_obj=n_obj,
-                    n_img=n_img)
+                    n_img=n_img, window_objects=hint.get("per_window_objects"))
 
     def _shared_plan_linear(self, bbox, sub_idx, obj_idx, P, hint, own, n_obj, n_img, obj_img):
         """``shared_plan`` with the LINEAR pairs split off (csrc/kernels_shared.hip, sixth identity; full scenes only: the host knows
@@ -120,15 +120,20 @@ class PlanMixin:
         self._xw_linear = (e_lin, e_obj)          # bench accounting: windows combined instead of convolved, per-object entries
         return dict(gather=gather_c, incl=incl_c, n_total=incl_c[Pt - 1:], pixrect=pixrect, bound=e_c + e_obj, entries=e_c + e_obj,
                     entries_real=e_c, window_entries=hint.get("per_window"), objects=True, P=P, n_obj=n_obj, n_img=n_img,
-                    gather_all=gather_all, incl_all=incl_all, entries_all=e_all + e_obj, entries_real_all=e_all, lin=lin)
+                    gather_all=gather_all, incl_all=incl_all, entries_all=e_all + e_obj, entries_real_all=e_all, lin=lin,
+                    window_objects=hint.get("per_window_objects"))
 
-    def window_major_rows(self, plan, P, n2):
+    def window_major_rows(self, plan, P, n2, bbox=None, obj_img=None):
         """Window-major row space of the shared fc1 (``csrc/kernels_shared.hip``): device group offsets, tile -> group table and the
         row ``dest[e]`` of every listed window (X entries behind the per-object rows of their group; a pseudo-pair's own windows
         ARE per-object rows).  Per-window entry counts come from the host when it knows them (full scenes,
-        ``DeviceScene.window_entries``); a pair subset costs one read-back."""
-        from .pairs import window_major_layout
+        ``DeviceScene.window_entries``); a pair subset costs one read-back.
+        With the second level and ``TUNING.compact_object_rows`` (``bbox`` / ``obj_img`` given) the row space is COMPACT: a group's
+        per-object rows are the ``n_img`` background rows of its window and the pseudo-pairs whose rectangle R_o holds the window;
+        ``prow`` [n2 * 64] names the row that holds a pseudo-pair's value at every window (``sgc_window_rows_compact``)."""
+        from .pairs import window_major_layout, window_object_counts
         dev = self.device
+        compact = bool(plan.get("objects")) and TUNING.compact_object_rows and bbox is not None and obj_img is not None and n2 > 0
         split = "gather_all" in plan                  # linear pairs split off: the rows are those of the list of ALL X windows
         gather = plan["gather_all"] if split else plan["gather"]
         counts = plan.get("window_entries")
@@ -136,13 +141,24 @@ class PlanMixin:
             E = int((plan["incl_all"] if split else plan["incl"])[P - 1]) if P else 0
             counts = torch.bincount((gather[:E] & 63).long(), minlength=64).cpu().numpy()
         E = int(np.asarray(counts).sum())
-        goff, tile_group = window_major_layout(counts, n2)
+        lead = n2                                     # per-object rows in front of a group's X entries
+        if compact:
+            objs = plan.get("window_objects")
+            if objs is None:                          # the host does not know the boxes (a pair subset / hand-made hint): one read-back
+                objs = window_object_counts(bbox.detach().cpu().numpy())
+            lead = plan["n_img"] + 2 * np.asarray(objs, dtype=np.int64)
+        goff, tile_group = window_major_layout(counts, lead)
         # ONE host-to-device copy for the four small tables: group offsets, first X row of every group, group ends, tile -> group
-        gend_h = (goff[:64].astype(np.int64) + n2 + np.asarray(counts, dtype=np.int64)).astype(np.int32)
-        tables = np.concatenate([goff.astype(np.int32), np.zeros(3, dtype=np.int32), (goff[:64].astype(np.int64) + n2).astype(np.int32), gend_h,
+        gend_h = (goff[:64].astype(np.int64) + lead + np.asarray(counts, dtype=np.int64)).astype(np.int32)
+        tables = np.concatenate([goff.astype(np.int32), np.zeros(3, dtype=np.int32), (goff[:64].astype(np.int64) + lead).astype(np.int32), gend_h,
                                  np.asarray(tile_group, dtype=np.int32)])          # 68 + 64 + 64 + tiles: every table 16-byte aligned
         tab_d = torch.from_numpy(tables).to(dev)
         goff_d, xbase, gend, tile_group_d = tab_d[:65], tab_d[68:132], tab_d[132:196], tab_d[196:]
+        prow = None
+        if compact:
+            prow = torch.empty(n2 * 64, dtype=torch.int32, device=dev)
+            _lib.check(self.lib.sgc_window_rows_compact(_lib.ptr(bbox), _lib.ptr(obj_img), n2 // 2, plan["n_img"], _lib.ptr(goff_d), _lib.ptr(prow),
+                                                        self._st()), "sgc_window_rows_compact")
         Et = E
         if split:
             Et = plan["entries_all"]
@@ -157,9 +173,12 @@ class PlanMixin:
         elif E > 0:
             cex = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
             skeys, order = torch.sort((gather[:E] & 63).long(), stable=True)
-            base = torch.from_numpy(goff[:64].astype(np.int64) + n2 - cex).to(dev)
+            base = torch.from_numpy(goff[:64].astype(np.int64) + lead - cex).to(dev)
             dest[order] = (base[skeys] + torch.arange(E, device=dev)).int()
-        if Et > E and kern:                          # the pseudo-pairs' own windows: row goff[w] + ps
+        if Et > E and compact:                       # the pseudo-pairs' own windows: their rows of the compact space
+            _lib.check(self.lib.sgc_window_rows_objects_compact(_lib.ptr(gather[E:]), Et - E, _lib.ptr(prow), P, _lib.ptr(dest[E:]), self._st()),
+                       "sgc_window_rows_objects_compact")
+        elif Et > E and kern:                        # the pseudo-pairs' own windows: row goff[w] + ps
             _lib.check(self.lib.sgc_window_rows_objects(_lib.ptr(gather[E:]), Et - E, _lib.ptr(goff_d), P, _lib.ptr(dest[E:]), self._st()),
                        "sgc_window_rows_objects")
         elif Et > E:
@@ -178,8 +197,10 @@ class PlanMixin:
                 pair_k = (plan["gather"][:Ec] >> 6).long()
                 first = lambda inc: torch.cat([inc.new_zeros(1), inc[:-1]]).long()
                 dest_conv = dest[torch.arange(Ec, device=dev) - first(plan["incl"])[pair_k] + first(plan["incl_all"])[pair_k]].contiguous()
+        # ``x_tab`` / ``x_first``: what sgc_fc1_windows_gemm_x16 takes as (goff, n_pseudo) - a group's first X row is x_tab[w] + x_first
         return dict(goff=goff_d, goff_host=goff, gend=gend, tile_group=tile_group_d, dest=dest, dest_conv=dest_conv,
-                    rows=int(goff[64]), E=E, E_total=Et, n2=n2)
+                    rows=int(goff[64]), E=E, E_total=Et, n2=n2, prow=prow, xbase=xbase, x_tab=xbase if compact else goff_d,
+                    x_first=0 if compact else n2)
 
     def _bucket_place(self, codes, n, sub_idx, obj_img, img_key, n_keys, base, out, seg, mode):
         """Stable placement of a window list by key (``sgc_bucket_place_seg``: two-level kernels, scratch from the workspace)."""

@@ -279,9 +279,18 @@ def window_entry_counts(bb: np.ndarray, img_ptr) -> np.ndarray:
     return out
 
 
-def window_major_layout(entry_counts: np.ndarray, n_pseudo: int):
-    """Group offsets of the window-major row space (``csrc/kernels_shared.hip``): group w = n_pseudo per-object rows + its X entries,
-    padded to a multiple of 256.  Returns (goff [65] int32, tile_group [rows/256] int32)."""
+def window_object_counts(bb: np.ndarray) -> np.ndarray:
+    """[64] number of objects whose window rectangle R_o holds each pooling window: in the compact window-major row space a window's
+    group has two pseudo-pair rows (o, bg), (bg, o) per such object."""
+    r = object_window_rects(bb)
+    wy, wx = np.divmod(np.arange(64), 8)
+    inside = (wx[None] >= r[:, 0:1]) & (wx[None] < r[:, 1:2]) & (wy[None] >= r[:, 2:3]) & (wy[None] < r[:, 3:4])
+    return inside.sum(0).astype(np.int64)
+
+
+def window_major_layout(entry_counts: np.ndarray, n_pseudo):
+    """Group offsets of the window-major row space (``csrc/kernels_shared.hip``): group w = n_pseudo per-object rows (one number, or
+    [64] per window: compact row space) + its X entries, padded to a multiple of 256.  Returns (goff [65] int32, tile_group [rows/256] int32)."""
     size = (n_pseudo + np.asarray(entry_counts, dtype=np.int64) + 255) // 256 * 256
     goff = np.concatenate([[0], np.cumsum(size)]).astype(np.int32)
     tile_group = np.repeat(np.arange(64, dtype=np.int32), (size // 256).astype(np.int64))
@@ -371,6 +380,7 @@ def flatten_scene(cfg, batch, device) -> DeviceScene:
                        shared_windows=count_shared_windows(bb, img_ptr) if (n_obj and F == 32) else None,
                        window_entries=window_entry_counts(bb, img_ptr) if (n_obj and F == 32) else None,
                        object_windows=count_object_windows(bb) if (n_obj and F == 32) else None,
+                       window_objects=window_object_counts(bb) if (n_obj and F == 32) else None,
                        linear_windows=count_linear_windows(bb, img_ptr) if (n_obj and F == 32) else None,
                        conv2_windows=count_conv2_windows(bb) if (n_obj and F == 32) else None,
                        _rel_src=getattr(batch, "relationships", None) if rel is not None else None)
