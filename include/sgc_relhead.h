@@ -365,6 +365,26 @@ int sgc_bayes_head_any_candidates(const float* h, const float* W, const float* b
  * indices (-1 padded), out_count [n_img]. */
 int sgc_topk_per_image(const float* conf, const int* seg_ptr, int n_img, int K, int* out_idx, int* out_count, void* stream);
 
+/* Scene-graph inference: the ranked top-K triples of every image straight from the forward's outputs, one workgroup per image
+ * (evaluator.py:125-134,160-194,292-316,465-503: candidate confidences + category confidences, overlap and commonsense filters,
+ * `confidence += connectivity`, per-image ranking, the fields of the ranked edge list).
+ * Candidate (pair p, slot s) of cand_conf / cand_pred [P][rep] (rep = 1 or 3) has confidence (cand_conf[p][s] + cat_conf[p]) + conn[p]
+ * in that f32 order; cat_conf [P] may be NULL; conn [P] is the log-sigmoid connectivity.  It is -inf where mask[p] == 0 (u8 [P] or
+ * NULL) or where the commonsense bitmaps (sgc_commonsense_filter's layout; both NULL = no filter) reject
+ * (cats[sub_idx[p]], cand_pred[p][s], cats[obj_idx[p]]).  Pairs with included[p] == 0 (u8 [P] or NULL) are no candidates at all.
+ * image_ptr [n_img+1] / pair_list [image_ptr[n_img]]: the pair rows of every image in ascending order (pair_list NULL = the rows
+ * image_ptr[b] .. image_ptr[b+1]-1 themselves).  sub_idx / obj_idx [P] (flattened object indices) and cats [n_obj] int64 may be NULL
+ * without bitmaps; out_sub / out_obj are then -1.
+ * Stable descending top-K, 1 <= K <= 128; ties in the reference's append order: slot_major = 0 (pair, slot) for fused scenes,
+ * slot_major = 1 (slot, pair) for one blocked append of all rows.  Outputs [n_img][K], padded with -1 / -inf: pair row, slot,
+ * predicate, subject and object object-index, score; out_count [n_img] = min(K, candidates), out_finite [n_img] = ranked entries
+ * with a finite score. */
+int sgc_scene_graph_topk(const float* cand_conf, const int* cand_pred, int rep, const float* cat_conf, const float* conn,
+                         const unsigned char* mask, const unsigned char* included, const int* image_ptr, const int* pair_list,
+                         const int* sub_idx, const int* obj_idx, const long* cats, const unsigned* aligned, const unsigned* violated,
+                         int C, int R, int n_img, int K, int slot_major, int* out_pair, int* out_slot, int* out_pred, int* out_sub,
+                         int* out_obj, float* out_score, int* out_count, int* out_finite, void* stream);
+
 /* Recall@K hit test (evaluator.py:306-356; Evaluator_Top3 :720-760 with n_pred = 3): for each of n_targets connected ground-truth
  * triples (t_row = row of its image in keep_pos; t_rel / t_scat / t_ocat int64; boxes f32 (x0,x1,y0,y1), int() truncation and slice
  * clipping applied inside) the rank of the first of the image's ranked candidates (keep_pos [n_img][K] flat positions, keep_cnt

@@ -360,6 +360,64 @@ def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred,
     return scene, out, included.cpu().numpy()
 
 
+def image_pair_lists(scene: DeviceScene):
+    """(ptr [B+1] int32, list [P] int32) on the device: the pair rows of every image in ascending order - the per-image view of
+    the step-major pair order that ``sgc_scene_graph_topk`` walks.  Derived once per scene (one stable device sort) and kept on it."""
+    cached = getattr(scene, "_image_pairs", None)
+    if cached is None:
+        n = np.asarray(scene.num_objects, dtype=np.int64)
+        ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(n * (n - 1))]).astype(np.int32)).to(scene.bbox.device)
+        cached = scene._image_pairs = (ptr, torch.sort(scene.image, stable=True)[1].to(torch.int32))
+    return cached
+
+
+def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool = True, commonsense=None, cat_confidence=None,
+                         scene: Optional[DeviceScene] = None, workspace_budget: Optional[float] = None):
+    """Image + objects in, the ranked top-``top_k`` (subject, predicate, object) triples of every image out (``scene_graph.SceneGraphs``,
+    device tensors; ``.to_list(heights, widths, names)`` gives the reference's ``predicted_graph``, ``evaluator.py:465-503``).
+    Needs no relation targets and no ``Evaluator``: the forward's outputs are ranked in place by one kernel
+    (``sgc_scene_graph_topk``), with the confidences, filters and tie order of ``evaluate_minibatch`` + ``Evaluator.compute()``
+    (``overlap_filtering``: a direction-step in which no image's boxes overlap contributes no candidates, a filtered pair's
+    candidates rank at -inf).  ``commonsense`` = (aligned, violated) triplet collections or a ``commonsense.TripletBitmaps``: the
+    ``eval_cs`` filter.  ``cat_confidence``: per-image lists of per-object category confidences, as ``evaluate_sgdet_minibatch``
+    takes them (subject + object confidence is added to every candidate of the pair).  A minibatch over ``workspace_budget`` is
+    scored in image groups like ``evaluate_minibatch``.  Everything the ranking needs besides the forward's outputs is put on the
+    device BEFORE the forward is enqueued; nothing after it synchronises with the host."""
+    from .commonsense import TripletBitmaps
+    from .scene_graph import attach_objects, rank_scene_graphs
+    cfg = model.head_config()
+    dev = next(model.parameters()).device
+    if scene is None:
+        scene = flatten_scene(cfg, batch, dev)
+    ptr, lst = image_pair_lists(scene)
+    raw = getattr(scene, "_bbox_raw_d", None)
+    if raw is None:
+        raw = scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(dev)
+    bitmaps = commonsense
+    if commonsense is not None and not isinstance(commonsense, TripletBitmaps):
+        bitmaps = model._commonsense_bitmaps(commonsense, dev)
+    cat_conf = None
+    if cat_confidence is not None:
+        conf_obj = torch.cat([torch.as_tensor(c).reshape(-1).to(dev, torch.float32) for c in cat_confidence])
+        if int(conf_obj.numel()) != int(scene.cats.numel()):
+            raise ValueError("cat_confidence must hold one value per object")
+        cat_conf = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+    iou = overlap_mask(scene) if overlap_filtering else None
+    included = _step_filter(scene, iou)[0] if overlap_filtering else None
+    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
+    if len(groups) > 1:
+        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, None)
+    else:
+        out = model.forward_pairs(scene, iou_mask=iou)
+    model.last_image_groups, model.last_outputs = groups, out
+    # torch's own log(sigmoid(x)), as the evaluator feed forms it: the ranked scores are bit for bit the evaluator's confidences
+    logsig = torch.log(torch.sigmoid(out.connectivity))
+    graphs = rank_scene_graphs(out.cand_conf, out.cand_pred, logsig, ptr, top_k=top_k, pair_list=lst, slot_major=False, cat_conf=cat_conf,
+                               mask=iou, included=included, sub_idx=scene.sub_idx, obj_idx=scene.obj_idx, cats=scene.cats, bitmaps=bitmaps)
+    graphs.image = torch.arange(int(ptr.numel()) - 1, dtype=torch.int32, device=dev)
+    return attach_objects(graphs, scene.cats, raw, cfg.feature_size)
+
+
 def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[DeviceScene] = None,
                     workspace_budget: Optional[float] = None, streams: Optional[int] = None, **loss_kw):
     """One optimisation step over all ordered pairs of the minibatch; returns the loss tensor.
