@@ -21,8 +21,6 @@ LIBNAME = "libsgc_relhead.so"
 ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
          "-I", CSRC, "-I", os.path.join(os.path.dirname(HERE), "include")]
-if os.environ.get("SGC_EXPERIMENTS") == "1":      # also compile the rejected main-loop variants (tools/gemm_microbench.py)
-    FLAGS.insert(5, "-DSGC_EXPERIMENTS")
 
 
 def hipcc() -> str:
@@ -79,7 +77,7 @@ def _headers_hash() -> str:
 
 
 def _compile(src: str, hdr_hash: str) -> str:
-    """One object per (source content, headers, flags): the object's name carries that hash, so a changed flag (``SGC_EXPERIMENTS``)
+    """One object per (source content, headers, flags): the object's name carries that hash, so a changed flag
     or header can never be satisfied by an object compiled under another one; older objects of the same source are removed."""
     import hashlib
     base = os.path.basename(src)[:-4]

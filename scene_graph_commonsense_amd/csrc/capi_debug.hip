@@ -1,4 +1,4 @@
-// Test hooks: raw access to the two GEMM engines (used by tests/test_gemm_gpu.py only).
+// Test hooks: raw access to the two GEMM engines (tests/test_gemm_gpu.py) and a few instruction probes.
 #include "gemm_nt.h"
 #include "gemm_tn.h"
 
@@ -13,67 +13,13 @@ int sgc_dbg_gemm_nt(int elem, const void* A, const void* B, void* C, int M, int 
     return launch_gemm_nt<ELEM_BF16, AMODE_PLAIN, EPI_STORE>(p, (hipStream_t)stream);
 }
 
-// ablation hook for tools/gemm_microbench.py (bf16, 256x256 block): abl as documented at gemm_nt_kernel
-int sgc_dbg_gemm_nt_abl(int abl, const void* A, const void* B, void* C, int M, int N, int K, void* stream) {
-    NtParams p{};
-    p.A = (const u16*)A; p.B = (const u16*)B; p.C = C; p.M = M; p.N = N; p.K = K;
-    p.lda = K; p.ldb = K; p.ldc = N;
-    if ((N % 256) || (K % 64)) return SGC_ERR_ARG;
-    switch (abl) {
-        case 0: return launch_gemm_nt_cfg<ELEM_BF16, AMODE_PLAIN, EPI_STORE, 2, 4, 4, 2, 0>(p, (hipStream_t)stream);
-        case 1: return launch_gemm_nt_cfg<ELEM_BF16, AMODE_PLAIN, EPI_STORE, 2, 4, 4, 2, 1>(p, (hipStream_t)stream);
-        case 2: return launch_gemm_nt_cfg<ELEM_BF16, AMODE_PLAIN, EPI_STORE, 2, 4, 4, 2, 2>(p, (hipStream_t)stream);
-        case 3: return launch_gemm_nt_cfg<ELEM_BF16, AMODE_PLAIN, EPI_STORE, 2, 4, 4, 2, 3>(p, (hipStream_t)stream);
-        case 5: return launch_gemm_nt_cfg<ELEM_BF16, AMODE_PLAIN, EPI_STORE, 2, 4, 4, 2, 5>(p, (hipStream_t)stream);
-        case 6: p.epi_lds = 1; return launch_gemm_nt_pp<ELEM_BF16, EPI_STORE, 0>(p, (hipStream_t)stream);
-        case 7: p.epi_lds = 1; return launch_gemm_nt_pp<ELEM_BF16, EPI_STORE, 1>(p, (hipStream_t)stream);
-#ifdef SGC_EXPERIMENTS      // rejected main-loop variants, built with SGC_EXPERIMENTS=1 only
-        case 4: return launch_gemm_nt_ring<ELEM_BF16, AMODE_PLAIN, EPI_STORE>(p, (hipStream_t)stream);
-        case 8: return launch_gemm_nt_w4<ELEM_BF16, EPI_STORE, 0>(p, (hipStream_t)stream);
-        case 9: return launch_gemm_nt_w4<ELEM_BF16, EPI_STORE, 1>(p, (hipStream_t)stream);
-        case 10: p.epi_lds = 1; return launch_gemm_nt_pp1<ELEM_BF16, EPI_STORE>(p, (hipStream_t)stream);
-#endif
-    }
-    return SGC_ERR_ARG;
-}
-
 // tools/stride_microbench.py: the ping-pong NT block with operand row pitches as parameters (do power-of-two pitches cost cache channels?)
 int sgc_dbg_gemm_nt_ld(const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, void* stream) {
     NtParams p{};
     p.A = (const u16*)A; p.B = (const u16*)B; p.C = C; p.M = M; p.N = N; p.K = K;
     p.lda = lda; p.ldb = ldb; p.ldc = N; p.epi_lds = 1;
     if ((N % 256) || (K % 64) || (lda % 8) || (ldb % 8)) return SGC_ERR_ARG;
-    return launch_gemm_nt_pp<ELEM_BF16, EPI_STORE, 0>(p, (hipStream_t)stream);
-}
-
-// tools/fc1_windows_microbench.py: the grouped fc1 product over window-major rows (sgc_fc1_windows_gemm) with the weight layout and the
-// epilogue as parameters.  mode 0: f32 tile in the MFMA's C layout (4-byte stores), 1: transposed tile (16-byte stores), 2: the same
-// without its stores (C ignored), 3: f16 output through the LDS-staged epilogue.
-int sgc_dbg_fc1_windows_gemm(const void* ywm, const void* w, const int* tile_group, void* owm, int rows, long ldb, long group_stride,
-                             long ldc, int mode, int stagger, int phases, unsigned long long* clk, void* stream) {
-    if (rows <= 0 || (rows & 255)) return SGC_ERR_ARG;
-    NtParams p{};
-    p.A = (const u16*)ywm; p.B = (const u16*)w; p.C = mode == 2 ? nullptr : owm; p.M = rows; p.N = 4096; p.K = 1024;
-    p.lda = 1024; p.ldb = ldb; p.ldc = ldc; p.tile_group = tile_group; p.group_stride = group_stride;
-    p.stagger = stagger; p.stagger_phases = phases; p.clk = clk;
-    switch (mode) {
-        case 0: return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32>(p, (hipStream_t)stream);
-        case 1: case 2: return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);
-        case 3: p.epi_lds = 1; return launch_gemm_nt_pp<ELEM_F16, EPI_STORE>(p, (hipStream_t)stream);
-        case 11: p.nt_store = 8; return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);      // tile-contiguous output
-        case 4: case 5: case 6: case 7: p.nt_store = mode - 3; return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);   // 1 with nt / sc1 / sc0 sc1 / sc0 sc1 nt
-    }
-    return SGC_ERR_ARG;
-}
-
-// tools/dgrad_patch_microbench.py: sgc_windows_dgrad_patches with the layouts as parameters (lda / seg_stride: elements between the
-// windows / between the own pixels of a window in dy3x; bpad: padding of B_pp's rows; split: 1 = the centre pixels in two slots of two combinations)
-int sgc_dbg_dgrad_patches(const void* dy3x, const void* w3patch, void* patch, int entries, long lda, long seg_stride, int bpad, int split,
-                          void* stream) {
-    NtParams p{};
-    p.A = (const u16*)dy3x; p.B = (const u16*)w3patch; p.C = patch; p.M = entries; p.N = (split ? 20 : 16) * 512; p.K = 4096;
-    p.lda = lda; p.ldb = 0; p.ldc = p.N; p.seg_stride = seg_stride; p.seg_bpad = bpad & 0xffff; p.patch_gn = bpad >> 16; p.seg_split = split;      // (bpad: low 16 bits = padding, high bits = patch width in virtual N tiles, 0 = default)
-    return launch_gemm_nt_pp_seg<ELEM_BF16>(p, (hipStream_t)stream);
+    return launch_gemm_nt_pp<ELEM_BF16, EPI_STORE>(p, (hipStream_t)stream);
 }
 
 // A: zero-padded channels-last images [n_img][S+2][S+2][Cin]; B: [N][Cin/64][9][64]; C: [n_img*S*S][N] window-major rows

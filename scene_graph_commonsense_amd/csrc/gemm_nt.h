@@ -51,11 +51,8 @@ struct NtParams {
     u16* Cx; int x_first;                           // nt_epilogue_f32t (fc1 over the window-major rows): rows whose index inside their group (row -
                                                     // wm_goff[tile_group[tile]]) is >= x_first - the pair-specific X rows - leave as f16 to Cx [M][N]
                                                     // instead of f32 to C; the per-object rows in front of them (2-D prefix sums follow) stay f32
-    int nt_store;                                   // nt_epilogue_f32t / nt_epilogue_store16: non-temporal stores (tools/fc1_windows_microbench.py)
-    unsigned long long* clk;                        // gemm_nt_pp_kernel (tools/fc1_windows_microbench.py): per-block wall clocks summed: [0] main loop, [1] epilogue, [2] blocks
-    long seg_stride; int seg_bpad, seg_split, patch_gn;                  // gemm_nt_pp_kernel<SEG>: elements between the segments (own pixels q) of a row of A; padding of B_pp's rows
-    int stagger, stagger_phases;                    // gemm_nt_pp_kernel: the blocks of the FIRST generation (one per CU) start (id/8 % phases) * stagger
-                                                    // sleep units (~4 us) late, so that the CUs' store phases do not coincide (0: off)
+    long seg_stride; int seg_bpad, seg_split;       // gemm_nt_pp_kernel<SEG>: elements between the segments (own pixels q) of a row of A; padding of B_pp's rows;
+                                                    // 1 = the four centre patch pixels in two slots of two combinations
 };
 
 template <int ELEM>
@@ -159,7 +156,7 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x16 (&acc)[TM]
 __device__ __forceinline__ void nt_epilogue_f32t(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane) {
     const int h = lane >> 5, cl = lane & 31;
     float* out = reinterpret_cast<float*>(p.C);
-    if (!out) return;                                  // tools/fc1_windows_microbench.py: the launch without its stores
+    if (!out) return;                                  // no output buffer: the launch without its stores
     const int g_first = p.Cx ? p.wm_goff[p.tile_group[m0 >> 8]] + p.x_first : 0;      // first X row of this tile's group
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -184,15 +181,6 @@ __device__ __forceinline__ void nt_epilogue_f32t(const NtParams& p, f32x16 (&acc
                     continue;
                 }
                 f32x4* dst = reinterpret_cast<f32x4*>(out + (long)row * p.ldc + col);
-#ifdef SGC_EXPERIMENTS      // tools/fc1_windows_microbench.py: tile-contiguous output, cache-policy bits of the store (1 nt, 2 sc1, 3 sc0 sc1, 4 sc0 sc1 nt)
-                if (p.nt_store == 8)
-                    dst = reinterpret_cast<f32x4*>(out + (((long)(m0 >> 8) * p.tiles_n + (n0 >> 8)) << 16) + ((row - m0) << 8) + (col - n0));
-                if (p.nt_store == 1) asm volatile("global_store_dwordx4 %0, %1, off nt" ::"v"(dst), "v"(v) : "memory");
-                else if (p.nt_store == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(v) : "memory");
-                else if (p.nt_store == 3) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" ::"v"(dst), "v"(v) : "memory");
-                else if (p.nt_store == 4) asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(dst), "v"(v) : "memory");
-                else
-#endif
                 *dst = v;
             }
         }
@@ -299,9 +287,7 @@ __device__ __forceinline__ void nt_epilogue_store16(const NtParams& p, f32x16 (&
 // Block configuration: WR x WC wavefronts, each owning a (TM*32) x (TN*32) output tile.
 //   small: 2x2 waves of 64x64   -> 128x128 block, 64 KiB LDS, 2 blocks/CU  (small problems, N % 256 != 0)
 //   big  : 2x4 waves of 128x64  -> 256x256 block, 128 KiB LDS, 1 block/CU  (half the LDS bytes per MFMA)
-// ABL (test hook only): 0 = normal; 1 = no global loads inside the K loop; 2 = no loads and no barriers;
-// 3 = loads and barriers only (no LDS reads / MFMA).  Used by tools/gemm_microbench.py to attribute time.
-template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN, int ABL = 0>
+template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN>
 __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NW = WR * WC;
@@ -354,11 +340,9 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams
         const long boff = (long)kt << 6;
         char* abase = smem + buf * BUF_BYTES + wid * (AI * 1024);
         char* bbase = smem + buf * BUF_BYTES + A_BYTES + wid * (BI * 1024);
-        if (ABL != 5 || (kt % 9) == 0) {       // ABL 5: A staged on one K tile in nine (timing model of halo reuse)
 #pragma unroll
-            for (int i = 0; i < AI; ++i)
-                __builtin_amdgcn_global_load_lds(GLB_PTR(a_ptr[i] + aoff), LDS_PTR(abase + i * 1024), 16, 0, 0);
-        }
+        for (int i = 0; i < AI; ++i)
+            __builtin_amdgcn_global_load_lds(GLB_PTR(a_ptr[i] + aoff), LDS_PTR(abase + i * 1024), 16, 0, 0);
 #pragma unroll
         for (int i = 0; i < BI; ++i)
             __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i] + boff), LDS_PTR(bbase + i * 1024), 16, 0, 0);
@@ -389,14 +373,11 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams
     const int nk = p.K >> 6;
     stage(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
-        if (ABL != 2) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-        }
-        if ((ABL == 0 || ABL == 3 || ABL == 5) && kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (kt + 1 < nk) stage((kt + 1) & 1, kt + 1);
         const char* ab = smem + (kt & 1) * BUF_BYTES;
         const char* bb = ab + A_BYTES;
-        if (ABL == 3) continue;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int c = ks * 2 + kh;
@@ -419,21 +400,14 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams
     else nt_epilogue<ELEM, EPI, TM, TN>(p, acc, m0, n0, wr, wc, lane);
 }
 
-#ifdef SGC_EXPERIMENTS
-inline int sgc_gemm_ring() { return sgc_tuning().gemm_ring; }      // 4-stage ring kernel (experiment; default off, see below)
-
-#endif
-
-inline int sgc_gemm_cfg() { return sgc_tuning().gemm_cfg; }        // forced block configuration (experiments only), common.h
-
-template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN, int ABL = 0>
+template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN>
 static int launch_gemm_nt_cfg(NtParams p, hipStream_t stream) {
     constexpr int BM = WR * TM * 32, BN = WC * TN * 32;
     constexpr int LDS0 = 2 * (BM + BN) * 128;
     constexpr int LDS = (EPI == EPI_STORE && TM == 4 && TN == 2 && WR * WC == 8 && LDS0 < EPI_LDS_BYTES) ? EPI_LDS_BYTES : LDS0;
     p.tiles_m = (p.M + BM - 1) / BM;
     p.tiles_n = p.N / BN;
-    auto kern = gemm_nt_kernel<ELEM, AMODE, EPI, WR, WC, TM, TN, ABL>;
+    auto kern = gemm_nt_kernel<ELEM, AMODE, EPI, WR, WC, TM, TN>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(WR * WC * 64), LDS, stream, p);
     SGC_CHECK_LAUNCH();
@@ -441,294 +415,25 @@ static int launch_gemm_nt_cfg(NtParams p, hipStream_t stream) {
 }
 
 
-#ifdef SGC_EXPERIMENTS
-// ---------------------------------------------------------------------------------------------------------------
-// 4-stage ring variant of the 256x256 block (BK = 32 per stage, 32 KiB per stage, 128 KiB LDS): global_load_lds for
-// stage kt+3 is issued while stage kt is being multiplied, a COUNTED s_waitcnt vmcnt leaves two stages in flight
-// across the raw s_barrier (a __syncthreads() would drain them).  Measured motivation (tools/gemm_microbench.py,
-// 32768x4096x8192 bf16): with the 2-stage loop the load round trip of one 64 KiB stage is 1.36 us against 1.5 us of
-// LDS-read + MFMA work per stage and the two overlap poorly (2.1 us per stage); the ring keeps 64-96 KiB of loads in
-// flight per CU.  RESULT: correct (tests run it with SGC_GEMM_CFG=3) but 5-10 % SLOWER than the 2-stage loop (995 vs
-// 1105 TFLOP/s on that GEMM; conv3 fwd 70.5 vs 69.0 ms): the load path is bandwidth- not latency-bound (loads-only
-// ablation: 12.4 TB/s of L2->LDS traffic), so deeper prefetch buys nothing and BK=32 doubles the barrier count.
-// Kept off by default as a documented experiment.  64-byte rows: chunk swizzle c ^ ((row>>2)&3) keeps the ds_read_b128 lane groups conflict-free.
-template <int ELEM, int AMODE, int EPI>
-__global__ __launch_bounds__(512, 2) void gemm_nt_ring_kernel(const NtParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int WR = 2, WC = 4, TM = 4, TN = 2, NS = 4;
-    constexpr int BM = 256, BN = 256;
-    constexpr int A_BYTES = BM * 64, B_BYTES = BN * 64, BUF_BYTES = A_BYTES + B_BYTES;   // 32 KiB per stage
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tn = blockIdx.x % p.tiles_n, tm = blockIdx.x / p.tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-
-    // loader: one instruction = 16 rows x 64 B; wave w stages rows w*32 .. w*32+31 of A and of B (2 + 2 instructions)
-    const int lrow = lane >> 2, cpos = lane & 3;
-    const u16* a_ptr[2];
-    const u16* b_ptr[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = wid * 32 + i * 16 + lrow;
-        const int chunk = cpos ^ ((row >> 2) & 3);
-        int m = m0 + row; if (m > p.M - 1) m = p.M - 1;
-        if constexpr (AMODE == AMODE_CONV) a_ptr[i] = p.A + conv_row_base(m, p.lgS, p.Cin) + chunk * 8;
-        else a_ptr[i] = p.A + (long)m * p.lda + chunk * 8;
-        b_ptr[i] = p.B + (long)(n0 + row) * p.ldb + chunk * 8;
-    }
-    const int Wp = (1 << p.lgS) + 2;
-    auto stage = [&](int buf, int kt) {            // kt counts 32-wide K tiles
-        long aoff;
-        if constexpr (AMODE == AMODE_CONV) {
-            const int k64 = kt >> 1;
-            const int cc = k64 / 9, tap = k64 - cc * 9;
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            aoff = (long)(ky * Wp + kx) * p.Cin + (cc << 6) + ((kt & 1) << 5);
-        } else {
-            aoff = (long)kt << 5;
-        }
-        const long boff = (long)kt << 5;
-        char* abase = smem + buf * BUF_BYTES + wid * 2048;
-        char* bbase = abase + A_BYTES;
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            __builtin_amdgcn_global_load_lds(GLB_PTR(a_ptr[i] + aoff), LDS_PTR(abase + i * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i] + boff), LDS_PTR(bbase + i * 1024), 16, 0, 0);
-        }
-    };
-
-    const int wr = wid / WC, wc = wid % WC;
-    const int kh = lane >> 5;
-    int a_off[TM], a_sw[TM], b_off[TN], b_sw[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int ra = wr * TM * 32 + i * 32 + (lane & 31);
-        a_off[i] = ra * 64; a_sw[i] = (ra >> 2) & 3;
-    }
-#pragma unroll
-    for (int i = 0; i < TN; ++i) {
-        const int rb = wc * TN * 32 + i * 32 + (lane & 31);
-        b_off[i] = rb * 64; b_sw[i] = (rb >> 2) & 3;
-    }
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int nk = p.K >> 5;
-    stage(0, 0);
-    if (nk > 1) stage(1, 1);
-    if (nk > 2) stage(2, 2);
-    for (int kt = 0; kt < nk; ++kt) {
-        // stage kt must have landed; the (up to) two younger stages stay in flight: 4 loads per stage per lane
-        if (kt + 2 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();              // every wave's share of stage kt is in LDS; stage kt-1 is fully consumed
-        if (kt + 3 < nk) stage((kt + 3) & 3, kt + 3);
-        const char* ab = smem + (kt & 3) * BUF_BYTES;
-        const char* bb = ab + A_BYTES;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const int c = ks * 2 + kh;
-            s16x8 af[TM], bf[TN];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(ab + a_off[i] + ((c ^ a_sw[i]) << 4));
-#pragma unroll
-            for (int i = 0; i < TN; ++i) bf[i] = *reinterpret_cast<const s16x8*>(bb + b_off[i] + ((c ^ b_sw[i]) << 4));
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = mfma32<ELEM>(af[i], bf[j], acc[i][j]);
-        }
-    }
-    nt_epilogue<ELEM, EPI, TM, TN>(p, acc, m0, n0, wr, wc, lane);
-}
-
-template <int ELEM, int AMODE, int EPI>
-static int launch_gemm_nt_ring(NtParams p, hipStream_t stream) {
-    constexpr int LDS = 4 * 512 * 64;
-    p.tiles_m = (p.M + 255) / 256;
-    p.tiles_n = p.N / 256;
-    auto kern = gemm_nt_ring_kernel<ELEM, AMODE, EPI>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
-    SGC_CHECK_LAUNCH();
-    return SGC_OK;
-}
-#endif  // SGC_EXPERIMENTS
-
-
-// ---------------------------------------------------------------------------------------------------------------
-// Halo-staged implicit 3x3 convolution for 16x16 maps (conv3 forward and data gradient): one workgroup = one image
-// (256 pixels) x 256 output channels.  For every 64-channel chunk the 18x18 zero-padded patch of the image is staged
-// in LDS ONCE (41 KiB) and the nine taps read their A fragments from it at shifted pixel rows; only the weight tile
-// (32 KiB) is staged per (chunk, tap).  L2->LDS traffic per K step falls from 64 KiB to 36.6 KiB (-43 %), which is
-// what limits the plain implicit GEMM (tools/gemm_microbench.py: the load stream and the LDS-read+MFMA loop overlap
-// poorly; staging A on one K tile in nine was measured +10 %).
-// Patch row r = py*18 + px (128 B per row); 16-B chunk swizzle c ^ f(py,px), f = ((px>>1) + 4*(py&1)) & 7, keeps every
-// ds_read_b128 lane group (pixels of windows {0,3,5,6} / {1,2,4,7} on two image rows) conflict-free for all nine taps.
-template <int ELEM, int EPI>
-__global__ __launch_bounds__(512, 2) void conv16_halo_kernel(const NtParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int WC = 4, TM = 4, TN = 2;
-    constexpr int A_BYTES = 328 * 128;            // 324 patch rows, padded to 41 x 8 rows
-    constexpr int B_BYTES = 256 * 128;
-    char* const abuf0 = smem;
-    char* const bbuf0 = smem + 2 * A_BYTES;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int tn = blockIdx.x % p.tiles_n, img = blockIdx.x / p.tiles_n;
-    const int m0 = img * 256, n0 = tn * 256;
-    const int Cin = p.Cin;
-
-    // ---- A patch loader: 41 instructions of 8 rows; wave w issues instructions w, w+8, ... (<= 6)
-    const int lrow = lane >> 3, cpos = lane & 7;
-    int a_off[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        int r = (wid + 8 * i) * 8 + lrow;
-        if (r > 323) r = 323;
-        const int py = r / 18, px = r - py * 18;
-        const int f = ((px >> 1) + 4 * (py & 1)) & 7;
-        a_off[i] = r * Cin + ((cpos ^ f) << 3);
-    }
-    const u16* const a_img = p.A + (long)img * (324L * Cin);
-    auto stage_a = [&](int buf, int cc) {
-        char* base = abuf0 + buf * A_BYTES;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int t = wid + 8 * i;
-            if (t < 41)
-                __builtin_amdgcn_global_load_lds(GLB_PTR(a_img + a_off[i] + (cc << 6)), LDS_PTR(base + t * 1024), 16, 0, 0);
-        }
-    };
-    // ---- B (weight) loader: as in the plain kernel
-    const u16* b_ptr[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = wid * 32 + i * 8 + lrow;
-        b_ptr[i] = p.B + (long)(n0 + row) * p.ldb + ((cpos ^ ((row >> 1) & 7)) << 3);
-    }
-    auto stage_b = [&](int buf, int step) {
-        char* base = bbuf0 + buf * B_BYTES + wid * 4096;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            __builtin_amdgcn_global_load_lds(GLB_PTR(b_ptr[i] + ((long)step << 6)), LDS_PTR(base + i * 1024), 16, 0, 0);
-    };
-
-    // ---- fragment addressing
-    const int wr = wid / WC, wc = wid % WC;
-    const int kh = lane >> 5;
-    int a_row[TM], a_px[TM], a_py[TM], b_off[TN], b_sw[TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int m = wr * 128 + i * 32 + (lane & 31);
-        const int W = m >> 2, q = m & 3;
-        a_py[i] = 2 * (W >> 3) + (q >> 1);
-        a_px[i] = 2 * (W & 7) + (q & 1);
-        a_row[i] = a_py[i] * 18 + a_px[i];
-    }
-#pragma unroll
-    for (int i = 0; i < TN; ++i) {
-        const int rb = wc * TN * 32 + i * 32 + (lane & 31);
-        b_off[i] = rb * 128; b_sw[i] = (rb >> 1) & 7;
-    }
-    f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-    const int ncc = Cin >> 6;
-    const int nsteps = ncc * 9;
-    stage_a(0, 0);
-    stage_b(0, 0);
-    int step = 0;
-    for (int cc = 0; cc < ncc; ++cc) {
-        const char* ab = abuf0 + (cc & 1) * A_BYTES;
-#pragma unroll 1
-        for (int tap = 0; tap < 9; ++tap, ++step) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (step + 1 < nsteps) stage_b((step + 1) & 1, step + 1);
-            if (tap == 0 && cc + 1 < ncc) stage_a((cc + 1) & 1, cc + 1);
-            const char* bb = bbuf0 + (step & 1) * B_BYTES;
-            const int ky = tap / 3, kx = tap - 3 * ky;
-            int ar[TM], af_sw[TM];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                ar[i] = (a_row[i] + ky * 18 + kx) * 128;
-                af_sw[i] = (((a_px[i] + kx) >> 1) + 4 * ((a_py[i] + ky) & 1)) & 7;
-            }
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const int c = ks * 2 + kh;
-                s16x8 af[TM], bf[TN];
-#pragma unroll
-                for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(ab + ar[i] + ((c ^ af_sw[i]) << 4));
-#pragma unroll
-                for (int i = 0; i < TN; ++i) bf[i] = *reinterpret_cast<const s16x8*>(bb + b_off[i] + ((c ^ b_sw[i]) << 4));
-#pragma unroll
-                for (int i = 0; i < TM; ++i)
-#pragma unroll
-                    for (int j = 0; j < TN; ++j) acc[i][j] = mfma32<ELEM>(af[i], bf[j], acc[i][j]);
-            }
-        }
-    }
-    if constexpr (EPI == EPI_STORE) {
-        if (p.epi_lds) { nt_epilogue_store16<ELEM>(p, acc, m0, n0, wr, wc, lane, wid, smem); return; }
-    }
-    nt_epilogue<ELEM, EPI, TM, TN>(p, acc, m0, n0, wr, wc, lane);
-}
-
-template <int ELEM, int EPI>
-static int launch_conv16_halo(NtParams p, hipStream_t stream) {
-    constexpr int LDS = 2 * 328 * 128 + 2 * 256 * 128;
-    p.tiles_m = p.M / 256;
-    p.tiles_n = p.N / 256;
-    auto kern = conv16_halo_kernel<ELEM, EPI>;
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
-    SGC_CHECK_LAUNCH();
-    return SGC_OK;
-}
-
 #include "gemm_nt_pp.h"
-#ifdef SGC_EXPERIMENTS      // main-loop variants that were measured and rejected (profiles/README.md); SGC_EXPERIMENTS=1 builds them
-#include "gemm_nt_w4.h"     // for tools/gemm_microbench.py - they are not part of the product library
-#include "gemm_nt_pp1.h"
-#endif
 
-inline int sgc_gemm_pp() { return sgc_tuning().gemm_pp; }          // ping-pong 256x256 loops (0: the 2-stage loops)
-inline int sgc_conv_halo() { return sgc_tuning().conv_halo; }      // halo-staged implicit convolution (0: plain implicit GEMM)
-
+// One schedule per shape and mode.  Outputs of M x N >= 256^3 elements with N % 256 == 0 take a 256x256 block: the halo-staged
+// ping-pong block for 3x3 convolutions on 16x16 maps, the ping-pong block for plain rows, the 2-stage block for the other
+// convolutions (conv2's 32x32 maps).  Everything else takes the 128x128 block.
 template <int ELEM, int AMODE, int EPI>
 static int launch_gemm_nt(NtParams p, hipStream_t stream) {
+    static_assert(AMODE == AMODE_PLAIN || AMODE == AMODE_CONV, "gathered rows have their own launchers");
     if (p.M <= 0) return SGC_OK;
     if ((p.K & 63) || (p.N & 127) || p.K <= 0) return SGC_ERR_ARG;
     if (AMODE == AMODE_CONV && ((p.Cin & 63) || p.K != 9 * p.Cin)) return SGC_ERR_ARG;
-    const int cfg = sgc_gemm_cfg();
-    p.epi_lds = sgc_tuning().epi_lds;      // 0 keeps the direct 2-byte stores
-    const bool big_ok = (p.N % 256) == 0;
+    p.epi_lds = 1;                         // 16-bit outputs of the 256x256 blocks leave through LDS as 16-byte stores
+    const bool big = (p.N % 256) == 0 && (long)p.M * p.N >= 256L * 256 * 256;
     if constexpr (AMODE == AMODE_CONV && (EPI == EPI_POOL || EPI == EPI_STORE)) {
-        if (p.lgS == 4 && big_ok && (p.M % 256) == 0 && (cfg == 4 || cfg == 7 || (cfg == 0 && sgc_conv_halo() && (long)p.M * p.N >= 256L * 256 * 256))) {
-            if (cfg == 7 || (cfg == 0 && sgc_gemm_pp())) return launch_conv16_halo_pp<ELEM, EPI>(p, stream);
-            return launch_conv16_halo<ELEM, EPI>(p, stream);
-        }
+        if (big && p.lgS == 4 && (p.M % 256) == 0) return launch_conv16_halo_pp<ELEM, EPI>(p, stream);
     }
-    const bool big = big_ok && (cfg == 2 || cfg == 3 || (cfg == 0 && (long)p.M * p.N >= 256L * 256 * 256));
-#ifdef SGC_EXPERIMENTS
-    if (big && (cfg == 3 || (cfg == 0 && sgc_gemm_ring()))) return launch_gemm_nt_ring<ELEM, AMODE, EPI>(p, stream);
-#endif
-    if constexpr (AMODE == AMODE_PLAIN) {
-        if (big_ok && (cfg == 5 || (big && cfg == 0 && sgc_gemm_pp()))) return launch_gemm_nt_pp<ELEM, EPI>(p, stream);
+    if (big) {
+        if constexpr (AMODE == AMODE_PLAIN) return launch_gemm_nt_pp<ELEM, EPI>(p, stream);
+        else return launch_gemm_nt_cfg<ELEM, AMODE, EPI, 2, 4, 4, 2>(p, stream);
     }
-    if (big) return launch_gemm_nt_cfg<ELEM, AMODE, EPI, 2, 4, 4, 2>(p, stream);
     return launch_gemm_nt_cfg<ELEM, AMODE, EPI, 2, 2, 2, 2>(p, stream);
 }

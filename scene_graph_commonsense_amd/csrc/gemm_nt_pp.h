@@ -4,7 +4,7 @@
 //  * The two waves that share a SIMD (w and w+4, i.e. the two wave ROWS wr = 0/1) run half a phase apart: while one
 //    issues its LDS fragment reads and its share of the global->LDS prefetch, the other issues MFMAs, and they swap at
 //    every s_barrier.  The 2-stage loop of gemm_nt_kernel leaves both waves of a SIMD reading LDS at the same time after
-//    each barrier (LDS-read + MFMA alone: 1450 TFLOP/s-equivalent there, 1555 here; tools/gemm_microbench.py).
+//    each barrier (LDS-read + MFMA alone: 1450 TFLOP/s-equivalent there, 1555 here).
 //  * A K tile is consumed in two phases = the two 64x64 halves of the wave's 128x64 output, 16 MFMAs per barrier slot:
 //    phase X (rows a0) reads the A0 half and both B halves (16 ds_read_b128), phase Y (rows a1) reads A1 (8).
 //  * Operands are staged in HALF tiles (128 rows x 64 k = 16 KiB = 2 global_load_lds per wave): A0/A1 = rows
@@ -78,7 +78,6 @@ __device__ __forceinline__ bool xcd_patch_map_aligned(int id, int tiles_m, int t
     return tm < tiles_m && w < gm * wn;
 }
 
-// ABL (tools/gemm_microbench.py only): 0 normal, 1 no global loads inside the K loop.
 // ACG = 1: the A operand is the implicit 3x3 convolution over a LIST of 2x2 windows of S x S maps, S = 16 or 32 (AMODE_CONV_GATHER of
 // gemm_nt.h: row m = pixel m&3 of window gather[m>>2] = image*(S/2)^2 + window, *gather_n entries, p.M only bounds the launch).  The rows of one
 // tile come from a few consecutive images (the list is sorted), so their byte offsets from the tile's first image fit the 32-bit
@@ -92,25 +91,18 @@ __device__ __forceinline__ bool xcd_patch_map_aligned(int id, int tiles_m, int t
 template <int ELEM, bool GATHER>
 __device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane,
                                                    int wid, char* smem, int m_limit);
-template <int ELEM, int EPI, int ABL = 0, int ACG = 0, int SEG = 0>
+template <int ELEM, int EPI, int ACG = 0, int SEG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int HT = 16384;                        // half-tile bytes; slot = parity*4 + kind, kind 0 A0, 1 B0, 2 B1, 3 A1
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wid >> 2, wc = wid & 3;
-#ifdef SGC_EXPERIMENTS      // tools/fc1_windows_microbench.py: staggered first generation of blocks, per-block wall clocks
-    if (p.stagger > 0 && blockIdx.x < 256) {          // equal tiles started together keep every CU's epilogue at the same moment
-        const int late = ((blockIdx.x >> 3) & (p.stagger_phases - 1)) * p.stagger;
-        for (int s = 0; s < late; ++s) __builtin_amdgcn_s_sleep(127);
-    }
-    const unsigned long long clk0 = p.clk ? wall_clock64() : 0ULL;
-#endif
     int tm, tn;
-    if (p.patch_aligned) {
+    if constexpr (SEG) {          // XCD patches of 16 M tiles x (slot, both channel halves): 7.37 against 7.50 ms for 4 x 8
+        xcd_patch_map(blockIdx.x, p.tiles_m, p.tiles_n, tm, tn, 16, 2);
+    } else if (p.patch_aligned) {
         if (!xcd_patch_map_aligned(blockIdx.x, p.tiles_m, p.tiles_n, tm, tn)) return;  // padding block (uniform exit)
-    } else if (SEG && p.patch_gn > 0) {
-        xcd_patch_map(blockIdx.x, p.tiles_m, p.tiles_n, tm, tn, 32 / p.patch_gn, p.patch_gn);      // tools/dgrad_patch_microbench.py: patch shape
     } else {
         xcd_patch_map(blockIdx.x, p.tiles_m, p.tiles_n, tm, tn);
     }
@@ -181,7 +173,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
         }
     }
     auto stage = [&](int kind, int t) __attribute__((always_inline)) {
-        if (ABL == 1 && t > 1) return;
         char* base = smem + (((t & 1) << 2) + kind) * HT + wid * 2048;
         const u16* g = (kind == 0 || kind == 3) ? a_blk : b_blk;
         int soff = t << 7;
@@ -291,16 +282,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
     if (stored) {
     } else if constexpr (EPI == EPI_STORE_F32T) {
         static_assert(!ACG, "transposed f32 tile: plain rows only");
-#ifdef SGC_EXPERIMENTS
-        const unsigned long long clk1 = p.clk ? wall_clock64() : 0ULL;
-#endif
         nt_epilogue_f32t(p, acc, m0, n0, wr, wc, lane);
-#ifdef SGC_EXPERIMENTS
-        if (p.clk && tid == 0) {                      // (wall clock: 100 MHz) time to ISSUE the stores, not to complete them
-            const unsigned long long clk2 = wall_clock64();
-            atomicAdd(p.clk, clk1 - clk0); atomicAdd(p.clk + 1, clk2 - clk1); atomicAdd(p.clk + 2, 1ULL);
-        }
-#endif
     }
     else if constexpr (ACG && EPI == EPI_POOL) {
         if (p.epi_lds) nt_epilogue_pool16<ELEM, true>(p, acc, m0, n0, wr, wc, lane, wid, smem, Mlim);
@@ -317,12 +299,11 @@ static int launch_gemm_nt_pp_conv_gather(NtParams p, hipStream_t stream) {
     if ((p.lgS != 4 && p.lgS != 5) || (p.Cin & 63) || p.K != 9 * p.Cin || (p.N & 255)) return SGC_ERR_ARG;
     p.tiles_m = (p.M + 255) / 256;
     p.tiles_n = p.N / 256;
-    const int al = sgc_tuning().acg_aligned;      // 1: grid padded to whole per-XCD patches
-    p.patch_aligned = al;
-    if (EPI == EPI_POOL) p.epi_lds = sgc_tuning().epi_lds;      // pooled rows through LDS to 16-byte row stores (nt_epilogue_pool16<.., GATHER>)
-    auto kern = gemm_nt_pp_kernel<ELEM, EPI, 0, 1>;
+    p.patch_aligned = 0;                    // the grid is sized for the bound, not for the list: no padding to whole per-XCD patches
+    if (EPI == EPI_POOL) p.epi_lds = 1;     // pooled rows through LDS to 16-byte row stores (nt_epilogue_pool16<.., GATHER>)
+    auto kern = gemm_nt_pp_kernel<ELEM, EPI, 1>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    SGC_LAUNCH(kern, dim3((unsigned)(al ? xcd_patch_grid(p.tiles_m, p.tiles_n) : p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
+    SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }
@@ -334,29 +315,27 @@ static int launch_gemm_nt_pp_seg(NtParams p, hipStream_t stream) {
     p.tiles_m = (p.M + 255) / 256;
     p.tiles_n = p.N / 256;                          // 32 or, with the centre pixels split, 40
     p.epi_lds = 1;
-    auto kern = gemm_nt_pp_kernel<ELEM, EPI_STORE, 0, 0, 1>;
+    auto kern = gemm_nt_pp_kernel<ELEM, EPI_STORE, 0, 1>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
-    const int grid_aligned = xcd_patch_grid(p.tiles_m, p.tiles_n), nb = p.tiles_m * p.tiles_n;
-    p.patch_aligned = (p.patch_gn == 0 && nb >= 1024 && (nb & 255) != 0 && grid_aligned * 10 <= nb * 11) ? 1 : 0;
-    SGC_LAUNCH(kern, dim3((unsigned)(p.patch_aligned ? grid_aligned : nb)), dim3(512), LDS, stream, p);
+    p.patch_aligned = 0;                            // the kernel walks 16 x 2 patches (see there)
+    SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }
 
-template <int ELEM, int EPI, int ABL = 0>
+template <int ELEM, int EPI>
 static int launch_gemm_nt_pp(NtParams p, hipStream_t stream) {
     constexpr int LDS = (EPI == EPI_STORE) ? EPI_LDS_BYTES : 8 * 16384;
     p.tiles_m = (p.M + 255) / 256;
     p.tiles_n = p.N / 256;
-    auto kern = gemm_nt_pp_kernel<ELEM, EPI, ABL>;
+    auto kern = gemm_nt_pp_kernel<ELEM, EPI>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     // whole patches per XCD only pay once every XCD has several of them; small grids keep the even spread of the contiguous walk
     const int grid_aligned = xcd_patch_grid(p.tiles_m, p.tiles_n);
-    const int al = sgc_tuning().nt_aligned;       // 0 / 1 forces, -1 = by grid size
     const int nb = p.tiles_m * p.tiles_n;
     // the contiguous walk is itself patch-aligned when every XCD's share is a multiple of 32 tiles (fc1 data gradient: 126 x 256
     // tiles, measured 1 % faster than the round-robin patches); otherwise pad, unless the grid is small or the padding > 10 %
-    p.patch_aligned = al >= 0 ? al : ((nb >= 1024 && (nb & 255) != 0 && grid_aligned * 10 <= nb * 11) ? 1 : 0);
+    p.patch_aligned = (nb >= 1024 && (nb & 255) != 0 && grid_aligned * 10 <= nb * 11) ? 1 : 0;
     SGC_LAUNCH(kern, dim3((unsigned)(p.patch_aligned ? grid_aligned : p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
@@ -451,8 +430,12 @@ __device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&a
 // Halo-staged implicit 3x3 convolution on 16x16 maps with the ping-pong schedule (conv3 forward / data gradient).
 // One workgroup = one image (256 pixels, window-major rows) x 256 output channels; K step = (64-channel chunk, tap).
 // The zero-padded 18x18x64 patch of a chunk is staged ONCE (41 KiB, double buffered) and the nine taps read their A
-// fragments from it at shifted pixel rows (see conv16_halo_kernel in gemm_nt.h for the swizzle); the weight tile is
-// staged per step as two half tiles B0/B1 in a four-slot ring (two steps).  LDS: 2 x 41 KiB + 4 x 16 KiB = 146 KiB.
+// fragments from it at shifted pixel rows; the weight tile is staged per step as two half tiles B0/B1 in a four-slot ring
+// (two steps).  LDS: 2 x 41 KiB + 4 x 16 KiB = 146 KiB.  L2->LDS traffic per K step falls from the 64 KiB of the plain implicit
+// GEMM to 36.6 KiB (-43 %), which is what limits that kernel (its load stream and its LDS-read + MFMA loop overlap poorly; staging
+// A on one K tile in nine was measured +10 %).
+// Patch row r = py*18 + px (128 B per row); 16-B chunk swizzle c ^ f(py,px), f = ((px>>1) + 4*(py&1)) & 7, keeps every
+// ds_read_b128 lane group (pixels of windows {0,3,5,6} / {1,2,4,7} on two image rows) conflict-free for all nine taps.
 // Per wave and step: phase Y issues the four weight loads of step s+2 (replacing what phase X(s) read) and, in the first
 // taps of a chunk, one piece of the NEXT chunk's patch; it ends with vmcnt(4 or 5): only its own loads may still be in
 // flight, so the weights of step s+1 and every older patch piece have landed.  Phase X issues nothing and has no vmcnt wait.
@@ -716,9 +699,8 @@ static int launch_conv16_halo_pp(NtParams p, hipStream_t stream) {
         // 28.7e6 - 45.5e6 KiB from run to run.  Launch time is the same within box noise (round 2: 60.2 vs 59.6 ms in one
         // alternated pair, 60.8 / 61.2 vs 60.9 / 61.0 in another; profiles/r02_halo_walk_ab.txt, r02_hook_sweep.txt) - the launch
         // is power-bound, not traffic-bound - so the forward keeps the walk with the lower, stable traffic.  A larger weight tile
-        // (conv3 data gradient: 4.7 MiB) thrashes either way and takes walk 1.  (SgcTuning::halo_walk forces, experiments only.)
-        const int hw = sgc_tuning().halo_walk;
-        p.halo_walk = hw >= 0 ? hw : ((long)p.K * 512 > (3L << 20) ? 1 : 0);
+        // (conv3 data gradient: 4.7 MiB) thrashes either way and takes walk 1.
+        p.halo_walk = (long)p.K * 512 > (3L << 20) ? 1 : 0;
     }
     if constexpr (ELEM == ELEM_BF16 && EPI == EPI_STORE) {
         if (p.Apool) {                                 // A operand given as pooled rows + routing byte: un-pooled inside the block

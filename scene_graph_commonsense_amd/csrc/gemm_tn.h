@@ -23,7 +23,7 @@ struct TnParams {
     int lgS, Cin;                // BMODE_CONV
     int CinA;                    // ACONV: A rows are the centre pixels of a zero-padded image with CinA channels
     int tiles_m, tiles_n, ktiles_per_split, splits;
-    int xcd_map;                 // conv3 wgrad only: XCD-aware tile assignment (see kernel)
+    int xcd_map;                 // conv3 wgrad only (4 x 18 tiles): XCD-aware tile assignment (see kernel)
     int xcd_patch;               // ping-pong block: per-XCD 4x8 tile patches (tile count per split divisible by 8)
     const int* gather;           // BMODE_GATHER: contraction row r = pixel r&3 of window gather[r>>2] = image*64 + window of 16x16 maps
                                  // [img][18][18][Cin] (csrc/kernels_shared.hip): the conv weight gradient over LISTED windows with no
@@ -202,10 +202,8 @@ static int launch_gemm_tn_cfg(TnParams p, int splits, int* slabs_out, hipStream_
     auto kern = gemm_tn_kernel<ELEM, BMODE, ACONV, WR, WC, TM, TN>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     p.splits = splits;
-    {
-        const int xm = sgc_tuning().tn_xcd;      // XCD-aware assignment of the 4 x 18 tile grid (measured -0.7 % time, 2.5x less fabric traffic)
-        p.xcd_map = (xm && BMODE == BMODE_CONV && p.tiles_m == 4 && p.tiles_n == 18) ? 1 : 0;
-    }
+    // XCD-aware assignment of the 4 x 18 tile grid (measured -0.7 % time, 2.5x less fabric traffic)
+    p.xcd_map = (BMODE == BMODE_CONV && p.tiles_m == 4 && p.tiles_n == 18) ? 1 : 0;
     SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n * splits)), dim3(WR * WC * 64), LDS, stream, p);
     SGC_CHECK_LAUNCH();
     if (slabs_out) *slabs_out = splits;
@@ -226,20 +224,7 @@ __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(const TnParams p) {
     const int wr = wid >> 2, wc = wid & 3;
     const int tiles = p.tiles_n * p.tiles_m;
     int split, tm, tn;
-    if (p.xcd_map == 3) {
-        // grouped form, 64 groups (window positions w = 8 row + col) of 64 tiles (round 6): ALL tiles of a group on ONE XCD - its 32 CUs share
-        // the group's rows of both operands through its L2 and every operand byte leaves the fabric once (tiles of a group dealt over the
-        // eight XCDs: every XCD fetched all of B and an eighth of A, 9.5 GB per step against 4.2 algorithmic).  Groups differ in length
-        // (centre windows are pair-specific more often than border windows): an XCD takes one window of every row and of every column.
-        // (second form, round 6: HALF a group - 8 M tiles x all 4 N tiles = 32 tiles, one round of the XCD's CUs - per unit, sixteen units
-        //  per XCD: the two halves of a group go to XCDs four apart, B leaves the fabric twice, A once.)
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;          // j = 0 .. 511: the XCD's sixteen units of 32 tiles
-        const int unit = j >> 5, t = j & 31;
-        const int half = unit & 1, row = unit >> 1;
-        split = row * 8 + ((xcd - row - 4 * half) & 7);
-        tm = half * 8 + (t >> 2);
-        tn = t & 3;
-    } else if (p.xcd_map) {
+    if (p.xcd_map) {
         const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
         split = j / 9;
         tm = xcd & 3;
@@ -422,15 +407,11 @@ static int launch_gemm_tn_pp(TnParams p, int splits, int* slabs_out, hipStream_t
     auto kern = gemm_tn_pp_kernel<ELEM, BMODE, ACONV>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     p.splits = splits;
-    {
-        const int xm = sgc_tuning().tn_xcd;
-        p.xcd_map = (xm && BMODE == BMODE_CONV && p.tiles_m == 4 && p.tiles_n == 18) ? 1 : 0;
-        const int xp = sgc_tuning().tn_patch;    // 0: 16x16 super-tiles instead of per-XCD 4x8 patches
-        // per-XCD 4(M) x 8(N) patches need M tiles to share: with 4 M tiles (weight gradient over the pair-specific windows, 4 x 18
-        // tiles x 7 splits) a patch is a whole tile column block and the 9 tiles an XCD gets per split straddle two of them - the
-        // 16 x 16 super-tile walk measured 7.61 vs 8.48 ms there (alternated twice in one box); grids with >= 8 M tiles keep the patches
-        p.xcd_patch = (xp && !p.xcd_map && ((p.tiles_m * p.tiles_n) & 7) == 0 && p.tiles_m >= 8) ? 1 : 0;
-    }
+    p.xcd_map = (BMODE == BMODE_CONV && p.tiles_m == 4 && p.tiles_n == 18) ? 1 : 0;
+    // per-XCD 4(M) x 8(N) patches need M tiles to share: with 4 M tiles (weight gradient over the pair-specific windows, 4 x 18
+    // tiles x 7 splits) a patch is a whole tile column block and the 9 tiles an XCD gets per split straddle two of them - the
+    // 16 x 16 super-tile walk measured 7.61 vs 8.48 ms there (alternated twice in one box); grids with >= 8 M tiles keep the patches
+    p.xcd_patch = (!p.xcd_map && ((p.tiles_m * p.tiles_n) & 7) == 0 && p.tiles_m >= 8) ? 1 : 0;
     SGC_LAUNCH(kern, dim3((unsigned)(p.tiles_m * p.tiles_n * splits)), dim3(512), LDS, stream, p);
     SGC_CHECK_LAUNCH();
     if (slabs_out) *slabs_out = splits;
@@ -452,20 +433,17 @@ static inline int tn_auto_splits(int tiles, int nk) {
     return best;
 }
 
+// The ping-pong 256x256 block for outputs of M x N >= 256 x 1024 elements whose shape it can tile, the 128x128 block below that.
 template <int ELEM, int BMODE, int ACONV = 0>
 static int launch_gemm_tn(TnParams p, int splits, int* slabs_out, hipStream_t stream) {
     if ((p.K & 63) || (p.N & 127) || (p.M & 127) || p.K <= 0) return SGC_ERR_ARG;
     if (BMODE == BMODE_CONV && ((p.Cin & 127) || p.N != 9 * p.Cin)) return SGC_ERR_ARG;
-    const int cfg = sgc_gemm_cfg();
-    const bool big_ok = (p.N % 256) == 0 && (p.M % 256) == 0 && (BMODE != BMODE_CONV || (p.Cin % 256) == 0);
-    const bool big = big_ok && (cfg == 2 || (cfg == 0 && (long)p.M * p.N >= 512L * 512));
     // the ping-pong block takes per-lane taps: conv weight gradients with Cin = 128 (N = 1152 -> 5 column tiles, the last half empty)
     const bool pp_ok = (p.M % 256) == 0 && (BMODE == BMODE_CONV ? (p.Cin % 128) == 0 : (p.N % 256) == 0);
-    if (pp_ok && (cfg == 5 || cfg == 7 || (cfg == 0 && sgc_gemm_pp() && (long)p.M * p.N >= 256L * 1024))) {
+    if (pp_ok && (long)p.M * p.N >= 256L * 1024) {
         if (splits <= 0) splits = tn_auto_splits((p.M / 256) * ((p.N + 255) / 256), p.K >> 6);
         return launch_gemm_tn_pp<ELEM, BMODE, ACONV>(p, splits, slabs_out, stream);
     }
-    if (splits <= 0) splits = tn_auto_splits(big ? (p.M / 256) * (p.N / 256) : (p.M / 128) * (p.N / 128), p.K >> 6);
-    if (big) return launch_gemm_tn_cfg<ELEM, BMODE, ACONV, 2, 4, 4, 2>(p, splits, slabs_out, stream);
+    if (splits <= 0) splits = tn_auto_splits((p.M / 128) * (p.N / 128), p.K >> 6);
     return launch_gemm_tn_cfg<ELEM, BMODE, ACONV, 2, 2, 2, 2>(p, splits, slabs_out, stream);
 }

@@ -545,12 +545,7 @@ int sgc_pair_expand_dense_windows(const void* U, const void* V, const int* img_p
                                   void* z_pad_f16, void* z_pad_bf16, unsigned char* amz, const int* pixel_rect, void* stream) {
     if (max_n > 150 || max_n < 1) return SGC_ERR_ARG;
     if (n_img <= 0) return SGC_OK;
-#ifdef SGC_EXPERIMENTS
-    static const int listed = [] { const char* e = getenv("SGC_EXPAND_LIST"); return e ? atoi(e) : 1; }();     // A/B: profiles/r05_expand_ab.txt
-#else
-    constexpr int listed = 1;
-#endif
-    if (listed && pixel_rect)
+    if (pixel_rect)          // the listed form whenever the rectangles are known (A/B against the dense walk: profiles/r05_expand_ab.txt)
         SGC_LAUNCH(pair_expand_dense_list_kernel, dim3(256, (max_n + EXPAND_JT - 1) / EXPAND_JT, n_img), dim3(512), 0, (hipStream_t)stream,
                    (const u16*)U, (const u16*)V, img_ptr, pid, pid_ld, (u16*)z_pad_f16, (u16*)z_pad_bf16, amz, pixel_rect);
     else
@@ -590,12 +585,8 @@ int sgc_fc2_labels_relu(const void* h1, const void* w2m, const float* b, const f
     p.A = (const u16*)h1; p.B = (const u16*)w2m; p.C = p_out; p.M = n_pairs; p.N = 512; p.K = 4096;
     p.lda = 4096; p.ldb = 4096; p.ldc = 512; p.bias = b; p.lsub = lsub; p.lobj = lobj; p.sub_idx = sub_idx;
     p.obj_idx = obj_idx; p.drop_enable = drop_enable; p.drop_seed = drop_seed; p.scale = 2.f;
-#ifdef SGC_EXPERIMENTS
-    static const int big = [] { const char* e = getenv("SGC_FC2_BIG"); return e ? atoi(e) : 1; }();       // A/B: profiles/r05_small_kernels.txt
-#else
-    constexpr int big = 1;
-#endif
-    if (big && n_pairs >= 16384) {          // N = 512: two column tiles; from 64 row tiles on the 256 x 256 ping-pong block (the size rule of launch_gemm_nt starts at 256^3 outputs)
+    if (n_pairs >= 16384) {                 // N = 512: two column tiles; from 64 row tiles on the 256 x 256 ping-pong block (the size rule of launch_gemm_nt
+                                            // starts at 256^3 outputs; A/B: profiles/r05_small_kernels.txt)
         p.epi_lds = 0;
         return launch_gemm_nt_pp<ELEM_F16, EPI_FC2>(p, (hipStream_t)stream);
     }

@@ -716,9 +716,9 @@ __global__ __launch_bounds__(256) void pair_contract_windows_kernel(const u16* _
 // copies are summed per (image, window) in f32 before they are rounded (fc1_gsum_compact_kernel).  On the benchmark's boxes 68.8 % of the
 // 65 536 pseudo rows were such copies: 14.6 % of the rows of all three fc1 GEMMs (profiles/r07_compact_rows_ab.txt).
 // Row pitch of the f32 products owm in floats: 4096 + 256 B.  With the power-of-two pitch every row of a 256 x 256 output tile starts
-// 16 KiB after the previous one and the tile's stores drain 10 % slower (tools/fc1_windows_microbench.py: 3.18 -> 2.86 ms per launch
-// with 16-byte stores; profiles/r03_fc1_windows_microbench*.txt).
-static inline int owm_pitch() { return sgc_tuning().owm_pitch; }     // 4160
+// 16 KiB after the previous one and the tile's stores drain 10 % slower (3.18 -> 2.86 ms per launch with 16-byte stores;
+// profiles/r03_fc1_windows_microbench*.txt).
+constexpr int OWM_PITCH = 4160;
 // ``prow`` (compact row space): the row of (ps, window) is prow[ps*64 + window] instead of goff[window] + ps
 __global__ __launch_bounds__(256) void fc1_integral_kernel(const float* __restrict__ owm, int pitch, const int* __restrict__ goff, int n2,
                                                            float* __restrict__ S, const int* __restrict__ prow) {
@@ -1506,8 +1506,7 @@ int sgc_conv3_relu_pool_windows(const void* z_pad, const void* w3r, const float*
     p.A = (const u16*)z_pad; p.B = (const u16*)w3r; p.C = y; p.M = max_entries * 4; p.N = 1024; p.K = 9 * 512;
     p.ldb = 9 * 512; p.ldc = 1024; p.lgS = 4; p.Cin = 512; p.bias = b3; p.argmax = argmax; p.C2 = (u16*)y_bf16;
     p.gather = gather; p.gather_n = gather_n;
-    if (sgc_tuning().gather_pp) return launch_gemm_nt_pp_conv_gather<ELEM_F16, EPI_POOL>(p, (hipStream_t)stream);
-    return launch_gemm_nt_cfg<ELEM_F16, AMODE_CONV_GATHER, EPI_POOL, 2, 4, 4, 2>(p, (hipStream_t)stream);
+    return launch_gemm_nt_pp_conv_gather<ELEM_F16, EPI_POOL>(p, (hipStream_t)stream);
 }
 
 int sgc_shared_windows_assemble(const int* bbox, const int* sub_idx, const int* obj_idx, int n_pairs, int n_obj, const void* y_obj,
@@ -1640,7 +1639,6 @@ int sgc_windows_dgrad_patches(const void* dy3x, const void* w3patch, void* patch
     NtParams p{};
     p.A = (const u16*)dy3x; p.B = (const u16*)w3patch; p.C = patch; p.M = entries; p.N = PATCH_SLOTS * 512; p.K = 4096;
     p.lda = 4 * 1024; p.ldb = 0; p.ldc = PATCH_SLOTS * 512; p.seg_stride = 1024; p.seg_bpad = 0; p.seg_split = 1;
-    p.patch_gn = 2;        // XCD patches of 16 M tiles x (slot, both channel halves): 7.37 against 7.50 ms for 4 x 8 (tools/dgrad_patch_microbench.py)
     return launch_gemm_nt_pp_seg<ELEM_BF16>(p, (hipStream_t)stream);
 }
 int sgc_windows_patch_sum(const void* patch, const int* bbox, const int* sub_idx, const int* obj_idx, const int* count_incl, int n_pairs,
@@ -1681,16 +1679,8 @@ int sgc_pair_contract_windows(const void* dz, const unsigned char* amz, const in
                               void* stream) {
     if (n_obj <= 0) return SGC_OK;
     const long items = (long)(n_obj + n_img) * 256;
-#ifdef SGC_EXPERIMENTS
-    static const int pipe = [] { const char* e = getenv("SGC_CONTRACT_PIPE"); return e ? atoi(e) : 1; }();      // A/B: profiles/r05_contract_pipe_ab.txt
-#else
-    constexpr int pipe = 1;
-#endif
-    if (pipe)
-        SGC_LAUNCH(pair_contract_windows_kernel<true>, dim3(grid_cap(items, 4, 262144)), dim3(256), 0, (hipStream_t)stream, (const u16*)dz, amz,
-               ptr, list, pixel_rect, img_ptr, role, n_real_pairs, n_obj, bg_maps, (u16*)dU_pad, items);
-    else
-        SGC_LAUNCH(pair_contract_windows_kernel<false>, dim3(grid_cap(items, 4, 262144)), dim3(256), 0, (hipStream_t)stream, (const u16*)dz, amz,
+    // the software-pipelined form (A/B against the plain loop: profiles/r05_contract_pipe_ab.txt)
+    SGC_LAUNCH(pair_contract_windows_kernel<true>, dim3(grid_cap(items, 4, 262144)), dim3(256), 0, (hipStream_t)stream, (const u16*)dz, amz,
                ptr, list, pixel_rect, img_ptr, role, n_real_pairs, n_obj, bg_maps, (u16*)dU_pad, items);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
@@ -1713,8 +1703,7 @@ int sgc_conv3_relu_pool_windows_wm(const void* z_pad, const void* w3r, const flo
     p.A = (const u16*)z_pad; p.B = (const u16*)w3r; p.C = ywm; p.M = max_entries * 4; p.N = 1024; p.K = 9 * 512;
     p.ldb = 9 * 512; p.ldc = 1024; p.lgS = 4; p.Cin = 512; p.bias = b3; p.argmax = argmax; p.C2 = (u16*)ywm_bf16;
     p.gather = gather; p.gather_n = gather_n; p.dest = dest;
-    if (sgc_tuning().gather_pp) return launch_gemm_nt_pp_conv_gather<ELEM_F16, EPI_POOL>(p, (hipStream_t)stream);
-    return launch_gemm_nt_cfg<ELEM_F16, AMODE_CONV_GATHER, EPI_POOL, 2, 4, 4, 2>(p, (hipStream_t)stream);
+    return launch_gemm_nt_pp_conv_gather<ELEM_F16, EPI_POOL>(p, (hipStream_t)stream);
 }
 // the same, also writing the accumulators (before bias / ReLU / pooling) of the entries e >= raw_first to raw[(e - raw_first)*4 + pixel]
 int sgc_conv3_relu_pool_windows_wm_raw(const void* z_pad, const void* w3r, const float* b3, const int* gather, const int* gather_n,
@@ -1727,16 +1716,15 @@ int sgc_conv3_relu_pool_windows_wm_raw(const void* z_pad, const void* w3r, const
     p.gather = gather; p.gather_n = gather_n; p.dest = dest; p.raw = raw; p.raw_first = raw_first;
     return launch_gemm_nt_pp_conv_gather<ELEM_F16, EPI_POOL>(p, (hipStream_t)stream);
 }
-int sgc_fc1_products_pitch(void) { return owm_pitch(); }
+int sgc_fc1_products_pitch(void) { return OWM_PITCH; }
 // owm [rows][pitch] f32 (columns 0..4095) = ywm [rows][1024] f16 * w1p[:, g*1024 .. +1024]^T, g = tile_group[row / 256]  (rows a multiple of 256)
 int sgc_fc1_windows_gemm(const void* ywm, const void* w1p, const int* tile_group, float* owm, int rows, void* stream) {
     if (rows <= 0) return SGC_OK;
     if (rows & 255) return SGC_ERR_ARG;
     NtParams p{};
     p.A = (const u16*)ywm; p.B = (const u16*)w1p; p.C = owm; p.M = rows; p.N = 4096; p.K = 1024;
-    p.lda = 1024; p.ldb = 65536; p.ldc = owm_pitch(); p.tile_group = tile_group; p.group_stride = 1024;
-    if (sgc_tuning().f32_swap) return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);
-    return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32>(p, (hipStream_t)stream);
+    p.lda = 1024; p.ldb = 65536; p.ldc = OWM_PITCH; p.tile_group = tile_group; p.group_stride = 1024;
+    return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);
 }
 // the same with the pair-specific rows (index inside their group >= n_pseudo) written as f16 to oxh [rows][4096] instead of f32 to owm: each
 // is one of the ~7 products a pair adds to 13 f32 prefix-sum vectors before its sum is rounded to f16 anyway (model.py:148: h1), and the
@@ -1747,13 +1735,13 @@ int sgc_fc1_windows_gemm_x16(const void* ywm, const void* w1p, const int* tile_g
     if (rows & 255) return SGC_ERR_ARG;
     NtParams p{};
     p.A = (const u16*)ywm; p.B = (const u16*)w1p; p.C = owm; p.M = rows; p.N = 4096; p.K = 1024;
-    p.lda = 1024; p.ldb = 65536; p.ldc = owm_pitch(); p.tile_group = tile_group; p.group_stride = 1024;
+    p.lda = 1024; p.ldb = 65536; p.ldc = OWM_PITCH; p.tile_group = tile_group; p.group_stride = 1024;
     p.Cx = (u16*)oxh; p.x_first = n_pseudo; p.wm_goff = goff;
     return launch_gemm_nt_pp<ELEM_F16, EPI_STORE_F32T>(p, (hipStream_t)stream);
 }
 int sgc_fc1_integral(const float* owm, const int* goff, int n_pseudo, float* S, void* stream) {
     if (n_pseudo <= 0) return SGC_OK;
-    SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, owm_pitch(), goff,
+    SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, OWM_PITCH, goff,
                n_pseudo, S, (const int*)nullptr);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
@@ -1775,7 +1763,7 @@ int sgc_fc1_assemble_ordered(const float* S, const float* owm, const int* bbox, 
                              const int* dest, int n_obj, const float* bias, int drop_enable, unsigned drop_seed, void* h1, int n_pairs,
                              const float* own_rect_sums, const int* pair_order, void* stream) {
     if (n_pairs <= 0) return SGC_OK;
-    SGC_LAUNCH(fc1_assemble_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, S, owm, owm_pitch(), bbox, sub_idx, obj_idx, count_incl, dest,
+    SGC_LAUNCH(fc1_assemble_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, S, owm, OWM_PITCH, bbox, sub_idx, obj_idx, count_incl, dest,
                n_obj, bias, drop_enable, drop_seed, 2.f, (u16*)h1, own_rect_sums, pair_order, (const u16*)nullptr);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
@@ -1786,7 +1774,7 @@ int sgc_fc1_assemble_x16(const float* S, const void* oxh, const int* bbox, const
                          const float* own_rect_sums, const int* pair_order, void* stream) {
     if (n_pairs <= 0) return SGC_OK;
     if (!oxh) return SGC_ERR_ARG;
-    SGC_LAUNCH(fc1_assemble_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, S, (const float*)nullptr, owm_pitch(), bbox, sub_idx, obj_idx,
+    SGC_LAUNCH(fc1_assemble_kernel, dim3(n_pairs), dim3(256), 0, (hipStream_t)stream, S, (const float*)nullptr, OWM_PITCH, bbox, sub_idx, obj_idx,
                count_incl, dest, n_obj, bias, drop_enable, drop_seed, 2.f, (u16*)h1, own_rect_sums, pair_order, (const u16*)oxh);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
@@ -1930,7 +1918,9 @@ int sgc_fc1_windows_wgrad(const void* gwm, const void* ywm_bf16, const int* goff
     p.A = (const u16*)gwm; p.B = (const u16*)ywm_bf16; p.C = dw; p.M = 4096; p.N = 1024; p.K = rows;
     p.lda = 4096; p.ldb = 1024; p.ldc = 65536; p.goff = goff;
     p.tiles_m = 16; p.tiles_n = 4; p.ktiles_per_split = 0; p.splits = 64; p.xcd_map = 0; p.xcd_patch = 1;
-    if (sgc_tuning().fc1_wgrad_group_xcd) { p.xcd_map = 3; p.xcd_patch = 0; }       // a group's 64 tiles on one XCD (gemm_tn.h)
+    // (whole or half groups per XCD instead of the 4 x 8 patches were measured and left out: 2.39 -> 2.77 ms and 2.37 -> 2.41 ms, the
+    //  step unchanged - the fabric traffic they save, 9.5 -> ~4.8 GB, was Infinity-Cache hits that cost the neighbours nothing;
+    //  profiles/r06_fc1_wgrad_xcd_ab.txt)
     auto kern = gemm_tn_pp_kernel<ELEM_BF16, BMODE_PLAIN, 0>;
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 16384);
     SGC_LAUNCH(kern, dim3(64 * 64), dim3(512), 8 * 16384, (hipStream_t)stream, p);
@@ -2023,7 +2013,7 @@ int sgc_shared_objects_fill_argmax(const int* bbox, const int* obj_img, int n_ob
 int sgc_fc1_integral_rows(const float* owm, const int* prow, int n_pseudo, float* S, void* stream) {
     if (n_pseudo <= 0) return SGC_OK;
     if (!prow) return SGC_ERR_ARG;
-    SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, owm_pitch(),
+    SGC_LAUNCH(fc1_integral_kernel, dim3((unsigned)(((long)n_pseudo * 4096 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, owm, OWM_PITCH,
                (const int*)nullptr, n_pseudo, S, prow);
     SGC_CHECK_LAUNCH();
     return SGC_OK;

@@ -9,16 +9,18 @@ import csv
 import re
 import sys
 
-# (row label, where it is enqueued, C-ABI entry point(s), bound, [kernel-name regexes])   - first match wins, in this order
+# (row label, where it is enqueued, C-ABI entry point(s), bound, [kernel-name regexes])   - first match wins, in this order.
+# gemm_nt_pp_kernel<ELEM, EPI, ACG, SEG> was <ELEM, EPI, ABL = 0, ACG, SEG> in statistics files taken before the ablation parameter
+# was dropped (profiles/README.md has the name map): the regexes accept both forms.
 ROWS = [
     ("conv3 forward over the listed windows (f16, ReLU + pool epilogue, rows gathered by the window list)", "engine_fwd.conv3_shared",
-     "sgc_conv3_relu_pool_windows_wm", "MFMA", [r"gemm_nt_pp_kernel<0, 3, 0, 1"]),
+     "sgc_conv3_relu_pool_windows_wm", "MFMA", [r"gemm_nt_pp_kernel<0, 3, (0, )?1, 0>"]),
     ("conv3 data gradient, real pairs' windows, patch form on the sparse matrix cores", "engine_bwd._conv3_backward_shared",
      "sgc_windows_dgrad_patches_sparse", "MFMA (sparse) / operand arrival", [r"gemm_nt_sp_kernel"]),
     ("conv3 weight gradient, real pairs' windows, sparse matrix cores (second operand gathered from the f16 maps)", "engine_bwd._conv3_backward_shared",
      "sgc_windows_wgrad_gather_sparse / _patch_sparse", "MFMA (sparse) / operand arrival", [r"gemm_tn_sp_kernel<[12]>"]),
     ("fc1 over the window-major rows: forward products", "engine_fwd.fc1_shared", "sgc_fc1_windows_gemm[_x16]", "MFMA, K = 1024",
-     [r"gemm_nt_pp_kernel<0, [78], 0, 0", r"gemm_nt_pp_kernel<0, 7"]),
+     [r"gemm_nt_pp_kernel<0, [78], (0, )?0, 0>", r"gemm_nt_pp_kernel<0, 7"]),
     ("fc1 weight gradient (grouped TN) + conv2 / conv3-object weight gradients", "engine_bwd._fc1_backward_rows / train_backward",
      "sgc_fc1_windows_wgrad, sgc_conv2_wgrad, sgc_conv3_wgrad[_sparse], sgc_windows_wgrad_patch", "MFMA", [r"gemm_tn_pp_kernel", r"gemm_tn_sp_kernel<0>", r"gemm_tn_kernel"]),
     ("fc1 data gradient (grouped NT), conv3 data gradient of the dense tail / objects, fc2, conv2, conv1 GEMMs", "engine_bwd / engine_fwd",
