@@ -575,6 +575,17 @@ int sgc_object_masked_maps_bwd(const void* da, const int* img_ptr, const int* bb
 int sgc_tanh_bwd(const float* dA, const void* a_img, void* dpre, long n, void* stream);
 int sgc_conv1_wgrad(const void* dpre, const void* x_bf16, float* slabs, int n_rows, int XC, int splits, int* n_slabs, void* stream);
 
+/* Input gradient of conv1_1 / conv1_2 (backward of model.py:139-140 on train_test.py:194-195's cat(image_feature, image_depth)):
+ *   dX[img][c][pix] = sum_role sum_k dpre_role[img*HW + pix][k] * W1_role[k][c],  c = 0..256, k = 0..127
+ * (csrc/kernels_inputgrad.hip: bf16 MFMA, f32 accumulation, one launch, fixed summation order - two runs give identical bits).
+ * dpre_a / dpre_b [n_img*HW][128] bf16 as sgc_tanh_bwd leaves them; wt_a / wt_b [CP][128] bf16 = W1^T with K contiguous, CP = 257 padded
+ * to a multiple of 32 (288) with zero padding rows; both pointers of a role NULL = role absent (at least one role is present).
+ * Outputs NCHW f32: out0 [n_img][C0][HW] = channels 0..C0-1, out1 [n_img][C1][HW] = channels C0..C0+C1-1 (NULL with C1 = 0), C0 + C1 = 257;
+ * accumulate = 1 adds into them.  HW a multiple of 32, operand pointers 16-byte aligned.  Padded channels are never stored.
+ * Never synchronises, owns no memory; bad arguments return SGC_ERR_ARG. */
+int sgc_conv1_dgrad(const void* dpre_a, const void* wt_a, const void* dpre_b, const void* wt_b, float* out0, int C0, float* out1, int C1,
+                    int n_img, int HW, int accumulate, void* stream);
+
 /* One-pass SGD with momentum and weight decay on one f32 parameter tensor (torch.optim.SGD semantics with dampening 0, no Nesterov:
  * the optimizer of train_test.py:99-100): g' = g + wd*w; buf = first_step ? g' : momentum*buf + g'; w -= lr*buf.
  * 16-byte aligned pointers take the float4 path, anything else a scalar one. */
@@ -647,6 +658,12 @@ int sgc_generic_fc1_bwd(const void* dh1, const float* y, const float* w1, int n_
 /* da (gradient wrt a, overwritten with the gradient wrt conv1's pre-activation) -> dw1 [2][C][2C+1], db1 [2][C]. */
 int sgc_generic_conv1_bwd(const float* feat, const float* depth, long stride_feat, long stride_depth, const int* img, const int* box, const float* a,
                           float* da, int n_pairs, int C, int F, float* dw1, float* db1, void* stream);
+/* Input gradient of the same conv1 (backward of model.py:139-140 through the masks of train_test.py:194-195) from dpre1 [n_pairs][F*F][2C] f32 as
+ * sgc_generic_conv1_bwd leaves it in ``da``: out0 [n_img][C0][F*F] = channels 0..C0-1, out1 [n_img][C1][F*F] = the rest (NULL with C1 = 0),
+ * C0 + C1 = 2C+1; a pair side adds inside its box to the image img[side][pair] (fused form: the minibatch's images; per-step form: the crops
+ * of ``both``, full boxes).  One thread per output element, pairs in order: deterministic.  accumulate = 1 adds into the outputs. */
+int sgc_generic_conv1_dgrad(const float* dpre1, const float* w1, const int* img, const int* box, int n_pairs, int C, int F, float* out0, int C0,
+                            float* out1, int C1, int n_img, int accumulate, void* stream);
 
 /* ----------------------------------------------------------------------------------------------- test hooks (raw GEMM engines) */
 int sgc_dbg_gemm_nt(int elem, const void* A, const void* B, void* C, int M, int N, int K, long lda, long ldb, long ldc, const float* bias, void* stream);

@@ -237,6 +237,34 @@ __global__ void generic_conv1_bwd_weight_kernel(const float* __restrict__ feat, 
     }
 }
 
+// Input gradient of conv1: dx[im][k][pix] = sum_side sum_{p: img[side][p] == im, pix inside box[side][p]} sum_c dpre1[p][pix][side*C+c] * W[side][c][k]
+// (the mask of train_test.py:194-195 passes the gradient inside the pair side's box only).  One thread per output element walks the pairs
+// of its image in pair order: no atomics, fixed summation order.  Channels 0..C0-1 go to out0 [n_img][C0][F*F], C0..C0+C1-1 to out1.
+__global__ void generic_conv1_dgrad_kernel(const float* __restrict__ dpre, const float* __restrict__ w, const int* __restrict__ img,
+                                           const int* __restrict__ box, int P, int C, int F, float* __restrict__ out0, int C0,
+                                           float* __restrict__ out1, int C1, int n_img, int accumulate) {
+    const int K = 2 * C + 1, C2 = 2 * C, FF = F * F;
+    const long n = (long)n_img * K * FF;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const int pix = (int)(i % FF);
+        const long r = i / FF;
+        const int k = (int)(r % K), im = (int)(r / K);
+        const int y = pix / F, x = pix - y * F;
+        float acc = 0.f;
+        for (int side = 0; side < 2; ++side)
+            for (int p = 0; p < P; ++p) {
+                if (img[side * P + p] != im) continue;
+                const int* bx = box + ((long)side * P + p) * 4;
+                if (x < bx[0] || x >= bx[1] || y < bx[2] || y >= bx[3]) continue;
+                const float* g = dpre + ((long)p * FF + pix) * C2 + side * C;
+                const float* wk = w + (long)side * C * K + k;
+                for (int c = 0; c < C; ++c) acc += g[c] * wk[(long)c * K];
+            }
+        float* dst = k < C0 ? out0 + ((long)im * C0 + k) * FF + pix : out1 + ((long)im * C1 + (k - C0)) * FF + pix;
+        *dst = accumulate ? *dst + acc : acc;
+    }
+}
+
 inline int grid_for(long n) { return (int)((n + 255) / 256 > 65535 * 16 ? 65535 * 16 : (n + 255) / 256 < 1 ? 1 : (n + 255) / 256); }
 
 }  // namespace
@@ -310,6 +338,17 @@ int sgc_generic_conv1_bwd(const float* feat, const float* depth, long stride_fea
     SGC_CHECK_LAUNCH();
     SGC_LAUNCH(generic_conv1_bwd_weight_kernel, dim3(grid_for((long)2 * C * (2 * C + 1))), dim3(256), 0, st, feat, depth, stride_feat, stride_depth, img,
                box, da, n_pairs, C, F, dw1, db1);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
+int sgc_generic_conv1_dgrad(const float* dpre1, const float* w1, const int* img, const int* box, int n_pairs, int C, int F, float* out0, int C0,
+                            float* out1, int C1, int n_img, int accumulate, void* stream) {
+    if (n_pairs < 0 || C <= 0 || F <= 0 || n_img < 0) return SGC_ERR_ARG;
+    if (out0 == nullptr || C0 <= 0 || C1 < 0 || (out1 == nullptr) != (C1 == 0) || C0 + C1 != 2 * C + 1) return SGC_ERR_ARG;
+    if (n_img == 0) return SGC_OK;
+    SGC_LAUNCH(generic_conv1_dgrad_kernel, dim3(grid_for((long)n_img * (2 * C + 1) * F * F)), dim3(256), 0, (hipStream_t)stream, dpre1, w1, img, box,
+               n_pairs, C, F, out0, C0, out1, C1, n_img, accumulate);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }

@@ -32,10 +32,13 @@ class BackwardMixin:
 
 
     def train_backward(self, ctx: "TrainContext", coefs, sub_csr, obj_csr, img_ptr, splits=8, grad_hook=None, dp_extra=None,
-                       cs_coef=None, upstream=None):
+                       cs_coef=None, upstream=None, input_grads=None):
         """Backward of the whole path.  Returns (loss scalar tensor, {reference parameter name: f32 gradient}).
         ``upstream=(g_rel, g_sup, g_conn, g_hidden)`` (``coefs`` None): no loss here - gradients of the outputs handed over by the
-        caller's autograd (per-step ``forward()``); the returned loss is None."""
+        caller's autograd (per-step ``forward()``); the returned loss is None.
+        ``input_grads``: None, or a dict of preallocated contiguous f32 device tensors that receive the gradient of the head's INPUTS
+        (``_conv1_input_grads``): ``feature`` [n_img,256,32,32] + ``depth`` [n_img,1,32,32] (+ ``accumulate``: add into both) on the fused
+        path, ``sub`` / ``obj`` [b,257,32,32] on the per-step path (``role_inputs``).  None: nothing here is launched or allocated."""
         lib, cfg, dev, w = self.lib, self.cfg, self.device, self.w
         ws = self.scratch              # everything allocated below is transient; what the forward kept lives in ``ctx`` / ``self.ws``
         P, Ppad, n_obj, n_img = ctx.P, ctx.Ppad, ctx.n_obj, ctx.n_img
@@ -134,7 +137,7 @@ class BackwardMixin:
                    "sgc_fc2_dgrad"))
 
         if getattr(ctx, "generic", None) is not None:        # sizes other than 128 / 32: the f32 per-pair trunk (engine_generic.py)
-            self._generic_trunk_backward(ctx, dh1, grads, side)
+            self._generic_trunk_backward(ctx, dh1, grads, side, input_grads)
             side.join()
             return loss, grads
 
@@ -223,10 +226,43 @@ class BackwardMixin:
                 if dcst_bg is not None:
                     dcst = dcst + dcst_bg
                 grads[nm + ".bias"] = self._colsum(dp1, n_img * 1024, 128, part_name=cpn) + dcst * (1 - tb * tb)
+        if input_grads is not None:
+            self._conv1_input_grads(ctx, input_grads)
         with side():
             grads["conv2_1.weight"] = gc2
         side.join()                              # the caller's stream continues only after every gradient is complete
         return loss, grads
+
+    def _conv1_input_grads(self, ctx, req):
+        """The other product of conv1's backward (``sgc_conv1_dgrad``): dX[img, c, pix] = sum_r sum_k dpre1_r[img*1024 + pix, k] * W1_r[k, c]
+        from the two ``dpre1_r`` [n_img*1024, 128] bf16 that ``sgc_tanh_bwd`` left in the scratch - every form of the backward (shared
+        windows or per pair, with or without the per-object second level) ends in them.  One launch on the caller's stream after both
+        roles exist; exactly zero outside the union of an image's boxes, where dA is zero.  Per-step contexts read a different input per
+        role: one launch per role, 257 channels each."""
+        lib, ws, n_img = self.lib, self.scratch, ctx.n_img
+        wd1 = self.w["wd1"]                                    # deferred copy (Weights): made at the first request after a weight change
+        dp = [ws.get("dpre1_%d" % r, n_img * 1024 * 128, torch.bfloat16) for r in (0, 1)]
+
+        def out(key, channels):
+            t = req[key]
+            if (t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
+                    or tuple(t.shape) != (n_img, channels, 32, 32)):
+                raise ValueError("input_grads[%r] must be a contiguous f32 [%d,%d,32,32] tensor on %s" % (key, n_img, channels, self.device))
+            return t
+        if "feature" in req:
+            if ctx.x[0] is not ctx.x[1]:
+                raise ValueError("input_grads feature / depth belong to the fused path; a per-step context takes sub / obj")
+            self._timed("conv1_dgrad", lambda: _lib.check(lib.sgc_conv1_dgrad(
+                _lib.ptr(dp[0]), _lib.ptr(wd1[0]), _lib.ptr(dp[1]), _lib.ptr(wd1[1]), _lib.ptr(out("feature", 256)), 256,
+                _lib.ptr(out("depth", 1)), 1, n_img, 1024, int(bool(req.get("accumulate", False))), self._st()), "sgc_conv1_dgrad"))
+        else:
+            for r, key in ((0, "sub"), (1, "obj")):
+                if req.get(key) is None:
+                    continue
+                a = (dp[0], wd1[0], None, None) if r == 0 else (None, None, dp[1], wd1[1])
+                self._timed("conv1_dgrad", lambda: _lib.check(lib.sgc_conv1_dgrad(
+                    _lib.ptr(a[0]), _lib.ptr(a[1]), _lib.ptr(a[2]), _lib.ptr(a[3]), _lib.ptr(out(key, 257)), 257, None, 0, n_img, 1024, 0,
+                    self._st()), "sgc_conv1_dgrad"))
 
     def _fc1_finish_wgrad(self, dW1p, dh1, Ppad, grads, grad_hook):
         """dW1p [4096][(window, channel)] -> the reference's column order (channel*64 + window), bias gradient, early all-reduce hook."""

@@ -19,6 +19,7 @@ from .synthetic import HeadConfig
 
 ELEM_F16, ELEM_BF16 = 0, 1
 XC = 384            # packed input channels (2*128+1 = 257 zero-padded to a multiple of the K tile)
+CP1 = 288           # rows of the transposed conv1 weight read by sgc_conv1_dgrad: 257 input channels padded to a multiple of 32
 
 
 def _c_long(v):
@@ -269,6 +270,7 @@ class _CheckRing:
 
 
 __all__ = [
+    "CP1",
     "Dict",
     "ELEM_BF16",
     "ELEM_F16",

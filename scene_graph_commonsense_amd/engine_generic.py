@@ -149,9 +149,10 @@ class GenericTrunkEngine(RelHeadEngine):
         ctx.p, ctx.out = self._fc2_head(ctx.h1, ctx.lsub, ctx.lobj, sub_idx, obj_idx, P, Ppad, dropout, seeds[1], keep=True)
         return ctx
 
-    def _generic_trunk_backward(self, ctx, dh1, grads: Dict[str, torch.Tensor], side):
+    def _generic_trunk_backward(self, ctx, dh1, grads: Dict[str, torch.Tensor], side, input_grads=None):
         """From dh1 (bf16, gradient wrt fc1's pre-activation) to the gradients of fc1, conv3, conv2, conv1 (``train_backward`` has done
-        the head and fc2).  Everything on the caller's stream: the shapes this path serves are launch-bound."""
+        the head and fc2).  Everything on the caller's stream: the shapes this path serves are launch-bound.  ``input_grads``: as
+        ``train_backward`` takes it, at this engine's sizes (``sgc_generic_conv1_dgrad``, plain f32)."""
         lib, w, cfg, dev, st = self.lib, self.w, self.cfg, self.device, self._st
         C, F, P = cfg.hidden_dim, cfg.feature_size, ctx.P
         H, Q = F // 2, (F // 4) ** 2
@@ -182,3 +183,34 @@ class GenericTrunkEngine(RelHeadEngine):
         for r, nm in enumerate(("conv1_1", "conv1_2")):
             grads[nm + ".weight"] = dw1[r].reshape(C, 2 * C + 1, 1, 1)
             grads[nm + ".bias"] = db1[r]
+        if input_grads is not None:
+            self._generic_input_grads(ctx, da, input_grads)
+
+    def _generic_input_grads(self, ctx, dpre1, req):
+        """``dpre1`` [P][F*F][2C] f32 (what ``sgc_generic_conv1_bwd`` left in ``da``) -> the gradient of the inputs: the minibatch's
+        feature / depth tensors (fused form: a pair side adds inside its box to its image), or the two crop stacks of the per-step form
+        (``_sides`` laid them out as one [2b, 2C+1, F, F] tensor, subject crops first)."""
+        lib, cfg, dev, g = self.lib, self.cfg, self.device, ctx.generic
+        C, F, P = cfg.hidden_dim, cfg.feature_size, ctx.P
+
+        def check(key, t, shape):
+            if t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+                raise ValueError("input_grads[%r] must be a contiguous f32 %s tensor on %s" % (key, list(shape), dev))
+            return t
+        if "feature" in req:
+            n_img = ctx.n_img
+            feat, depth = check("feature", req["feature"], (n_img, 2 * C, F, F)), check("depth", req["depth"], (n_img, 1, F, F))
+            _lib.check(lib.sgc_generic_conv1_dgrad(_lib.ptr(dpre1), _lib.ptr(self.w["g_w1"]), _lib.ptr(g["img"]), _lib.ptr(g["box"]), P, C, F,
+                                                   _lib.ptr(feat), 2 * C, _lib.ptr(depth), 1, n_img, int(bool(req.get("accumulate", False))),
+                                                   self._st()), "sgc_generic_conv1_dgrad")
+            return
+        # per-step form: ``_sides`` numbered the subject crops 0..P-1 and the object crops P..2P-1; a requested stack is written in place
+        # through an image table of its own in which the other side matches no image
+        ids = torch.arange(P, dtype=torch.int32, device=dev)
+        none = torch.full_like(ids, -1)
+        for key, img in (("sub", (ids, none)), ("obj", (none, ids))):
+            if req.get(key) is None:
+                continue
+            out = check(key, req[key], (P, 2 * C + 1, F, F))
+            _lib.check(lib.sgc_generic_conv1_dgrad(_lib.ptr(dpre1), _lib.ptr(self.w["g_w1"]), _lib.ptr(torch.stack(img).contiguous()), _lib.ptr(g["box"]),
+                                                   P, C, F, _lib.ptr(out), 2 * C + 1, None, 0, P, 0, self._st()), "sgc_generic_conv1_dgrad")

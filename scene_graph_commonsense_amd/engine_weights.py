@@ -138,6 +138,16 @@ class WeightsMixin:
                 return self._transpose_cast(g("fc1.weight").contiguous(), "w1pT", torch.bfloat16, 1, 64, 1024, 64 * 65536, 64, 65536,
                                             64, 4096, 1024 * 4096)
         w.defer("w1pT", make_w1pT)
+
+        # conv1_{1,2}.weight transposed, [2][CP][128] with K contiguous and zero padding rows: the A operand of the conv1 INPUT gradient
+        # (sgc_conv1_dgrad).  Deferred: made - and read - only by a backward that was asked for input gradients.
+        def make_wd1():
+            wd1 = self.ws.get("wd1", 2 * CP1 * 128, torch.bfloat16)                # created zeroed; the channel padding stays zero
+            with torch.no_grad():
+                for r, name in enumerate(("conv1_1.weight", "conv1_2.weight")):
+                    self._permute_cast(g(name).contiguous(), wd1, 1, [257, 128], [1, 257], [128, 1], dst_off=r * CP1 * 128)
+            return wd1.view(2, CP1, 128)
+        w.defer("wd1", make_wd1)
         if not TUNING.weight_kernels:
             return self._prep_bwd_trunk_weights_torch(g)
         c2, c3 = g("conv2_1.weight").contiguous(), g("conv3_1.weight").contiguous()

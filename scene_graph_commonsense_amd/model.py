@@ -61,8 +61,9 @@ class _PairStepFunction(torch.autograd.Function):
     """The reference's per-step classifier call (``train_utils.py:26-27``: b pre-masked subject / object crops) as ONE autograd
     node: forward = the HIP trunk + head on a child engine that keeps its context alive, backward = the HIP backward driven by
     the gradients of the outputs (``sgc_head_bwd_upstream``), so the reference's own ``training()`` - hundreds of calls, then
-    one ``losses.backward()`` (``train_test.py:189-276``) - trains the f32 master parameters.  The inputs get no gradient (the
-    reference computes them under ``no_grad``, ``train_test.py:154-156``)."""
+    one ``losses.backward()`` (``train_test.py:189-276``) - trains the f32 master parameters.  ``h_sub`` / ``h_obj`` get their gradient
+    (``sgc_conv1_dgrad``, in their own dtype and on their own device) when they require one; the reference's own crops, computed
+    under ``no_grad`` (``train_test.py:154-156``), do not, and then nothing extra is launched."""
 
     @staticmethod
     def forward(ctx, module, h_sub, h_obj, c1, c2, s1, s2, seeds, *params):
@@ -81,6 +82,7 @@ class _PairStepFunction(torch.autograd.Function):
         tctx = eng.train_forward(None, None, ids, full, c1.to(dev).long().contiguous(), mh1, ids, ids, seeds=seeds, dropout=module.training,
                                  role_inputs=(hs, ho), cats_obj=c2.to(dev).long().contiguous(), super_mh_obj=mh2)
         ctx.eng, ctx.tctx, ctx.module = eng, tctx, module
+        ctx.in_meta = tuple((tuple(h.shape), h.dtype, h.device) for h in (h_sub, h_obj))
         ctx.names = [n for n, _ in module.named_parameters()]
         ctx.csr = (torch.arange(b + 1, dtype=torch.int32, device=dev), ids)
         ctx.img_ptr = torch.arange(b + 1, dtype=torch.int32, device=dev)
@@ -96,11 +98,20 @@ class _PairStepFunction(torch.autograd.Function):
             raise RuntimeError("parameters changed between the per-step forward and its backward (optimizer.step() before "
                                "losses.backward()?): the 16-bit weight copies of the forward are gone")
         hier = module.hierarchical
+        req = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:     # h_sub / h_obj come from something trainable
+            req = {key: torch.empty(meta[0], dtype=torch.float32, device=ctx.eng.device)
+                   for key, meta, need in zip(("sub", "obj"), ctx.in_meta, ctx.needs_input_grad[1:3]) if need}
         _, grads = ctx.eng.train_backward(ctx.tctx, None, ctx.csr, ctx.csr, ctx.img_ptr,
-                                          upstream=(g_rel, g_sup if hier else None, g_conn.reshape(-1), g_hidden))
+                                          upstream=(g_rel, g_sup if hier else None, g_conn.reshape(-1), g_hidden), input_grads=req)
         ctx.eng = ctx.tctx = None                                  # free the step's buffers
         named = dict(module.named_parameters())
-        return (None,) * 8 + tuple(grads[n].view_as(named[n]) for n in ctx.names)
+        g_in = [None, None]
+        if req is not None:
+            for k, key in enumerate(("sub", "obj")):
+                if key in req:
+                    g_in[k] = req[key].to(device=ctx.in_meta[k][2], dtype=ctx.in_meta[k][1])
+        return (None, g_in[0], g_in[1]) + (None,) * 5 + tuple(grads[n].view_as(named[n]) for n in ctx.names)
 
 
 class _RelationBase(nn.Module):
@@ -250,7 +261,7 @@ class _RelationBase(nn.Module):
                       grad_hook=None, reducer=None, image_feature_aug: Optional[torch.Tensor] = None, lambda_contrast: float = 1.0,
                       commonsense=None, lambda_commonsense: float = 1.0, lambda_cs_weak: float = 0.1,
                       lambda_cs_strong: float = 10.0, loss_coefs=None, grads_out: Optional[Dict[str, torch.Tensor]] = None,
-                      engine: Optional[RelHeadEngine] = None, coupled: Optional[dict] = None):
+                      engine: Optional[RelHeadEngine] = None, coupled: Optional[dict] = None, input_grads=False):
         """Forward + loss + backward over all ordered pairs; gradients land in ``param.grad`` (accumulating like
         autograd).  Loss follows ``train_test.py:189-258`` / ``train_utils.py:64-157`` (hierarchical NLL, BCE on
         connectivity, running-sum step weights).  With ``image_feature_aug`` (DETR features of the colour-jittered view,
@@ -269,7 +280,13 @@ class _RelationBase(nn.Module):
         pieces, then this step per group): dict(seeds=(main, aug) - the dropout seeds of the group's first forward, so that this
         pass reproduces it bit for bit -, cs_coef [P, n_cand] or None - this group's rows of the minibatch's commonsense
         coefficients -, contrast=(dF_main [M, 512], dF_aug [M, 512]) or None - this group's rows of the SupCon feature gradient,
-        M = its connected pairs in pair order).  The loss returned then lacks the contrastive term (the caller adds it once)."""
+        M = its connected pairs in pair order).  The loss returned then lacks the contrastive term (the caller adds it once).
+        ``input_grads``: True - ``self.last_input_grads = {"image_feature": [B,2C,F,F] f32, "image_depth": [B,1,F,F] f32,
+        "image_feature_aug": tensor or None}`` holds d loss / d input of the returned loss (step weights, commonsense and contrastive
+        terms included; the augmented view's trunk writes its own feature gradient and adds its share to the depth gradient), exactly
+        zero outside the union of an image's boxes; or such a dict of preallocated contiguous tensors to write into (image groups hand
+        in their slices of the minibatch's).  They are this rank's images' gradients: a ``reducer`` does not touch them.  False
+        (default): nothing is launched or allocated for them."""
         # a reducer that is also the optimizer (distributed.ShardedSGD after ``attach``) may want fc1.weight's gradient in GEMM order on
         # EVERY path that feeds it - also these direct calls (gradient accumulation: zero_grad, several training_step, step)
         eng = engine if engine is not None else self.refresh_weights(backward=True)
@@ -278,7 +295,7 @@ class _RelationBase(nn.Module):
             try:
                 return self.training_step(scene, relationships, subj_or_obj, directed, lambda_connectivity, lambda_not_connected, class_weight,
                                           grad_hook, reducer, image_feature_aug, lambda_contrast, commonsense, lambda_commonsense,
-                                          lambda_cs_weak, lambda_cs_strong, loss_coefs, grads_out, engine, coupled)
+                                          lambda_cs_weak, lambda_cs_strong, loss_coefs, grads_out, engine, coupled, input_grads)
             finally:
                 eng.fc1_grad_gemm_order = False
         if reducer is not None:
@@ -286,6 +303,12 @@ class _RelationBase(nn.Module):
         cfg = self.head_config()
         dev = eng.device
         P = scene.n_pairs
+        ig = self._input_grad_buffers(scene, image_feature_aug, input_grads, dev) if input_grads else None
+        self.last_input_grads = ig
+        if ig is not None and P == 0:              # nothing reaches the inputs
+            for t in ig.values():
+                if t is not None:
+                    t.zero_()
         if P == 0 and grads_out is not None:       # an image group without pairs adds nothing to the minibatch's gradient sum
             self.last_outputs = None
             self.last_connectivity_stats = None
@@ -350,11 +373,16 @@ class _RelationBase(nn.Module):
                 dp_main[conn_idx] = dF_main
             loss, grads = eng.train_backward(ctx, coefs_d, sub_csr, obj_csr, img_ptr,
                                              grad_hook=grad_hook if extra is None else None, dp_extra=dp_main,
-                                             cs_coef=cs_coef)
+                                             cs_coef=cs_coef,
+                                             input_grads=None if ig is None else dict(feature=ig["image_feature"], depth=ig["image_depth"]))
+            if ig is not None and ig["image_feature_aug"] is not None:
+                ig["image_feature_aug"].zero_()            # no connected pair: stays zero; else the augmented trunk adds into it
             if extra is not None:
                 eng_a = extra["engine"]
                 _, grads_a = eng_a.train_backward(extra["ctx"], extra["coefs"], extra["sub_csr"], extra["obj_csr"], img_ptr,
-                                                  dp_extra=extra["dp_aug"])
+                                                  dp_extra=extra["dp_aug"],
+                                                  input_grads=None if ig is None else dict(feature=ig["image_feature_aug"],
+                                                                                           depth=ig["image_depth"], accumulate=True))
                 for k in grads:
                     grads[k] = grads[k] + grads_a[k].view_as(grads[k])
                 if grad_hook is not None:
@@ -381,6 +409,17 @@ class _RelationBase(nn.Module):
             self.last_connectivity_stats = eng.connectivity_stats(ctx.out.connectivity, directed_d, raw_d)
         self.last_outputs = ctx.out
         return loss
+
+    def _input_grad_buffers(self, scene, image_feature_aug, request, dev):
+        """The tensors ``training_step(input_grads=...)`` writes: the caller's (a dict, checked by the engine) or fresh ones."""
+        B, C2, F = int(scene.image_feature.shape[0]), 2 * self.input_dim, self.feature_size
+        if isinstance(request, dict):
+            if image_feature_aug is not None and request.get("image_feature_aug") is None:
+                raise ValueError("input_grads lacks the tensor for image_feature_aug")
+            return dict(image_feature=request["image_feature"], image_depth=request["image_depth"],
+                        image_feature_aug=request.get("image_feature_aug") if image_feature_aug is not None else None)
+        new = lambda c: torch.empty(B, c, F, F, dtype=torch.float32, device=dev)
+        return dict(image_feature=new(C2), image_depth=new(1), image_feature_aug=new(C2) if image_feature_aug is not None else None)
 
     def accumulate_grads(self, grads, eng):
         """``param.grad`` += the step's gradients (like autograd).  fc1.weight's carries its column order: the reference's, or the GEMM's
@@ -457,7 +496,8 @@ class _RelationBase(nn.Module):
         """(relation [b,R], super [b,3] | None, connectivity [b,1], hidden [b,512]) of one per-step call.  With autograd on
         and trainable parameters the call is an autograd node (``_PairStepFunction``); otherwise the inference trunk."""
         params = [p for _, p in self.named_parameters()]
-        if torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        wants = any(torch.is_tensor(h) and h.requires_grad for h in (h_sub, h_obj))      # crops from a trainable module, saliency
+        if torch.is_grad_enabled() and (wants or any(p.requires_grad for p in params)):
             seeds = self._next_seeds() if self.training else (0, 0)
             rel, sup, conn, pred = _PairStepFunction.apply(self, h_sub, h_obj, c1, c2, s1, s2, seeds, *params)
             return rel, (sup if self.hierarchical else None), conn, pred

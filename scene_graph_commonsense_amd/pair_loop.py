@@ -419,8 +419,13 @@ def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool 
 
 
 def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[DeviceScene] = None,
-                    workspace_budget: Optional[float] = None, streams: Optional[int] = None, **loss_kw):
+                    workspace_budget: Optional[float] = None, streams: Optional[int] = None, input_grads: bool = False, **loss_kw):
     """One optimisation step over all ordered pairs of the minibatch; returns the loss tensor.
+    ``input_grads=True``: ``model.last_input_grads`` holds d loss / d ``image_feature`` / ``image_depth`` / ``image_feature_aug`` of the
+    whole minibatch (``model.training_step``; image groups write their own image slices, images without pairs get zeros; local to
+    this rank with a ``reducer``), and a batch tensor that requires grad is driven backwards with it (``torch.autograd.backward``)
+    after the head's backward and before ``optimizer.step()``: whatever produced the features - an adapter, the encoder - then has
+    its ``.grad`` as after ``loss.backward()`` and can share the optimizer.
     A minibatch whose fused pass would exceed ``workspace_budget`` (bytes; default ``model.workspace_budget_bytes`` or 70 % of
     the free HBM) is run in consecutive image groups: whole-minibatch loss coefficients first, then forward + backward per group
     with its rows of them, the gradients summed and reduced across ranks once.  Equal to the one-pass step up to f32 summation
@@ -473,9 +478,9 @@ def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[
         if fuse_eng is not None:
             fuse_eng.fc1_grad_gemm_order = True
         if len(groups) == 1:
-            loss = model.training_step(scene, batch.relationships, batch.subj_or_obj, reducer=reducer, **loss_kw)
+            loss = model.training_step(scene, batch.relationships, batch.subj_or_obj, reducer=reducer, input_grads=bool(input_grads), **loss_kw)
         else:
-            loss = _train_image_groups(model, cfg, batch, scene, groups, reducer, loss_kw, lanes=lanes)
+            loss = _train_image_groups(model, cfg, batch, scene, groups, reducer, loss_kw, lanes=lanes, input_grads=bool(input_grads))
     except BaseException:
         # a GEMM-order gradient that may already hang on fc1.weight is a view of the engine's scratch in an order nobody else reads
         fc1 = getattr(model, "fc1", None)
@@ -487,6 +492,8 @@ def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[
         if fuse_eng is not None:
             fuse_eng.fc1_grad_gemm_order = False
     model.last_scene = scene
+    if input_grads:
+        _drive_input_autograd(batch, loss_kw.get("image_feature_aug"), model.last_input_grads)
     if optimizer is not None:
         try:
             optimizer.step()
@@ -497,6 +504,17 @@ def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[
                 fc1.weight._sgc_grad_gemm_order = False
             raise
     return loss
+
+
+def _drive_input_autograd(batch, aug, grads):
+    """Hand the head's input gradients to the autograd graph that produced the minibatch's tensors (those that require grad)."""
+    roots, gs = [], []
+    for t, g in ((batch.image_feature, grads["image_feature"]), (batch.image_depth, grads["image_depth"]), (aug, grads["image_feature_aug"])):
+        if torch.is_tensor(t) and t.requires_grad and g is not None:
+            roots.append(t)
+            gs.append(g.to(device=t.device, dtype=t.dtype).view_as(t))
+    if roots:
+        torch.autograd.backward(roots, gs)
 
 
 _LANE_STREAMS = {}
@@ -559,11 +577,18 @@ def _coupled_terms(model, cfg, batch, scene: DeviceScene, groups, subs, aug, com
     return out, loss_c
 
 
-def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, loss_kw, lanes: int = 1):
+def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, loss_kw, lanes: int = 1, input_grads: bool = False):
     from .engine import PairOutputs
     dev = scene.bbox.device
     kw = dict(loss_kw)
     aug, commonsense = kw.pop("image_feature_aug", None), kw.pop("commonsense", None)
+    ig = None
+    if input_grads:                                 # minibatch-sized; every group writes its own image slice (zeros where it has no pairs)
+        ig = {"image_feature": torch.zeros_like(scene.image_feature), "image_depth": torch.zeros_like(scene.image_depth),
+              "image_feature_aug": torch.zeros_like(scene.image_feature) if aug is not None else None}
+        w = model.refresh_weights(backward=True).w
+        if lanes > 1 and "wd1" in w.deferred:       # deferred copy: made on the caller's stream, before the lanes' streams read it
+            w["wd1"]
     lam = dict(lambda_contrast=kw.pop("lambda_contrast", 1.0), lambda_commonsense=kw.pop("lambda_commonsense", 1.0),
                lambda_cs_weak=kw.pop("lambda_cs_weak", 0.1), lambda_cs_strong=kw.pop("lambda_cs_strong", 10.0))
     coupled_terms = aug is not None or commonsense is not None
@@ -609,6 +634,8 @@ def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, 
             extra = {}
             if coupled is not None:
                 extra = dict(coupled=coupled[gi], image_feature_aug=None if aug is None else aug[a:b])
+            if ig is not None:
+                extra["input_grads"] = {k: (None if t is None else t[a:b]) for k, t in ig.items()}
             ln["loss"] = ln["loss"] + model.training_step(sub, sub_b.relationships, sub_b.subj_or_obj,
                                                           loss_coefs=tuple(c[rows] for c in coefs), grads_out=ln["acc"],
                                                           engine=ln["engine"] if coupled is None else None, **extra, **kw)
@@ -650,4 +677,5 @@ def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, 
     if not getattr(reducer, "owns_grads", False):
         model.accumulate_grads(acc, lane[0]["engine"])
     model.last_outputs, model.last_connectivity_stats = full, stats
+    model.last_input_grads = ig
     return loss

@@ -370,8 +370,8 @@ def flatten_scene(cfg, batch, device) -> DeviceScene:
                                         _lib.ptr(t["image"]), _lib.ptr(t["directed"]), _lib.ptr(t["raw"]), _lib.ptr(t["pid"]),
                                         _lib.ptr(t["obj_ptr"]), _lib.ptr(t["sub_list"]), _lib.ptr(t["obj_list"]), _lib.ptr(t["obj_img"]),
                                         _lib.ptr(t["step_ptr"]), _lib.stream_ptr()), "sgc_scene_tables")
-    return DeviceScene(image_feature=batch.image_feature.to(dev, torch.float32).contiguous(),
-                       image_depth=batch.image_depth.to(dev, torch.float32).contiguous(),
+    return DeviceScene(image_feature=batch.image_feature.detach().to(dev, torch.float32).contiguous(),
+                       image_depth=batch.image_depth.detach().to(dev, torch.float32).contiguous(),
                        obj_img=t["obj_img"][:n_obj], bbox=bbox_d, cats=cats_d, super_mh=mh_d, sub_idx=t["sub_idx"], obj_idx=t["obj_idx"],
                        step=t["step"], image=t["image"], directed=t["directed"] if rel is not None else None,
                        raw_target=t["raw"] if rel is not None else None, img_ptr=img_ptr_d, pid=t["pid"].view(max(n_obj, 1), pid_ld),
