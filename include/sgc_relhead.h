@@ -395,6 +395,22 @@ int sgc_recall_hits(const long* c_scat, const long* c_ocat, const long* c_pred, 
                     const long* t_ocat, const float* t_sbox, const float* t_obox, int n_targets, const unsigned char* equiv, int n_equiv,
                     int feature_size, double iou_thresh, int* hit, void* stream);
 
+/* Commonsense candidate mining of run_mode prepare_cs (evaluator.py:375-416, `_get_related_top_k_predictions` up to the LLM query):
+ * per image the ranked candidates that share an endpoint with a connected ground-truth triple.  Candidates and ranking in
+ * sgc_recall_hits' layout (flat int64 / f32 [n_cand] arrays, keep_pos [n_img][K] flat positions in ranked order, keep_cnt [n_img]);
+ * 1 <= top_k <= K <= 128.  t_ptr [n_img+1]: the CONNECTED targets of image b, in accumulation order, are rows t_ptr[b] ..
+ * t_ptr[b+1]-1 of t_scat / t_ocat (int64) and t_sbox / t_obox (f32 [.][4]); box arrays 16-byte aligned.  The reference's loop as
+ * written: for every target, ranks j = 0 .. min(top_k, keep_cnt)-1 in order; a candidate whose (subject class, subject box) or
+ * (object class, object box) equals the target's - by value, all four box entries - and whose (subject class, predicate, object
+ * class) was not accepted before is accepted; `count >= 10` ends the scan of a target and is tested after EVERY rank, so later
+ * targets look at rank 0 only (at most 11 edges; the `count >= 15` test before a target never fires).  -inf candidates take part.
+ * out_pos / out_rank [n_img][16]: flat candidate position and rank j of the accepted edges in acceptance order, -1 padded;
+ * out_count [n_img]; out_conf [n_img][16] (may be NULL; needs c_conf) = c_conf[out_pos], NaN padded.  One wavefront per image. */
+int sgc_related_topk(const long* c_scat, const long* c_ocat, const long* c_pred, const float* c_sbox, const float* c_obox,
+                     const float* c_conf, int n_cand, const int* keep_pos, const int* keep_cnt, int K, int top_k, const int* t_ptr,
+                     const long* t_scat, const long* t_ocat, const float* t_sbox, const float* t_obox, int n_img, int* out_pos,
+                     int* out_rank, int* out_count, float* out_conf, void* stream);
+
 /* "iou_mask" of testing(): the two boxes overlap on the FxF grid   (train_test.py:403-408).  bbox [n_obj][4], out u8 [n_pairs]. */
 int sgc_overlap_filter(const int* bbox, const int* sub_idx, const int* obj_idx, unsigned char* out, int n_pairs, void* stream);
 

@@ -3,8 +3,14 @@
 The reference tests ``tuple(triplet) in dict`` per candidate row on the host (a device->host copy and a Python
 hash lookup per row).  Here the two triplet sets become device bitmaps over the num_classes x num_relations x
 num_classes space (150*50*150 bits = 141 KB) and the filter is one HIP kernel over all candidates.
+
+``TripletSets`` is the producer of those two sets: step 2 of ``run_mode prepare_cs`` (reference ``dataloader.py:168-244``), the
+bookkeeping that turns the judged edges of the candidate mining (``Evaluator.get_related_top_k_predictions_parallel``) into the
+commonsense-aligned and -violated triplet dictionaries.  Host code, once per image.
 """
 from __future__ import annotations
+
+import os
 
 import numpy as np
 import torch
@@ -41,3 +47,76 @@ class TripletBitmaps:
                                               _lib.ptr(self.aligned), _lib.ptr(self.violated), self.C, self.R,
                                               _lib.stream_ptr()), "sgc_commonsense_filter")
         return confidence
+
+
+def _first_equal_box(box, bbox):
+    """Index of the FIRST object whose box equals ``box`` in all entries, or None (reference ``utils.match_bbox``, 'pc' branch)."""
+    box = torch.as_tensor(box)
+    for idx, b in enumerate(bbox):
+        if torch.sum(torch.abs(b - box)) == 0:
+            return idx
+    return None
+
+
+class TripletSets:
+    """The three dictionaries {(subject class, predicate, object class): count} of ``prepare_cs`` step 2 (``dataloader.py:53-57``)."""
+
+    def __init__(self):
+        self.triplets_train_gt = {}
+        self.commonsense_aligned_triplets = {}
+        self.commonsense_violated_triplets = {}
+        self._finalized = False
+
+    def add_image(self, categories, relationships, subj_or_obj, bbox, aligned_edges, violated_edges):
+        """One image (``dataloader.py:168-218``): ``categories`` [n], ``relationships`` / ``subj_or_obj`` its triangular target lists
+        (row i = object i+1 against objects 0..i; direction 1 = object i+1 is the subject, 0 = the object, anything else = no edge),
+        ``bbox`` [n,4], and the two saved edge lists of the mining ([subject_bbox, relation_id, object_bbox, confidence, j]).  An edge
+        counts under the classes of the FIRST objects whose boxes equal its two boxes exactly; it is skipped when both ends match the
+        same index or either end matches none."""
+        if self._finalized:
+            raise RuntimeError("finalize() has merged the ground truth already")
+        cat = lambda i: int(categories[i])
+        for i, (rels, sos) in enumerate(zip(relationships, subj_or_obj)):
+            for j, (rel, so) in enumerate(zip(rels, sos)):
+                if so == 1:
+                    key = (cat(i + 1), int(rel), cat(j))
+                elif so == 0:
+                    key = (cat(j), int(rel), cat(i + 1))
+                else:
+                    continue
+                self.triplets_train_gt[key] = self.triplets_train_gt.get(key, 0) + 1
+        for edges, table in ((aligned_edges, self.commonsense_aligned_triplets), (violated_edges, self.commonsense_violated_triplets)):
+            for subject_bbox, relation_id, object_bbox, _, _ in edges:
+                s, o = _first_equal_box(subject_bbox, bbox), _first_equal_box(object_bbox, bbox)
+                if s == o or s is None or o is None:
+                    continue
+                key = (cat(s), relation_id, cat(o))
+                table[key] = table.get(key, 0) + 1
+
+    def finalize(self):
+        """``save_all_triplets``' merge (``dataloader.py:226-233``), once: the ground-truth counts are added into the aligned set and
+        every ground-truth key is removed from the violated set."""
+        if not self._finalized:
+            for k, v in self.triplets_train_gt.items():
+                self.commonsense_aligned_triplets[k] = self.commonsense_aligned_triplets.get(k, 0) + v
+            self.commonsense_violated_triplets = {k: v for k, v in self.commonsense_violated_triplets.items()
+                                                  if k not in self.triplets_train_gt}
+            self._finalized = True
+        return self
+
+    def save(self, directory, llm_model):
+        """The two ``.pt`` dicts under the reference's names (``dataloader.py:239-244``); returns (aligned path, violated path)."""
+        self.finalize()
+        suffix = "_gpt4v" if llm_model == "gpt4v" else "_gpt3p5_temp"
+        os.makedirs(directory, exist_ok=True)
+        pa = os.path.join(directory, "commonsense_aligned_triplets%s.pt" % suffix)
+        pv = os.path.join(directory, "commonsense_violated_triplets%s.pt" % suffix)
+        torch.save(self.commonsense_violated_triplets, pv)
+        torch.save(self.commonsense_aligned_triplets, pa)
+        return pa, pv
+
+    def bitmaps(self, device, num_classes: int = 150, num_relations: int = 50) -> "TripletBitmaps":
+        """The device filter of ``train_cs`` / ``eval_cs`` straight from the sets, without the file round trip."""
+        self.finalize()
+        return TripletBitmaps(self.commonsense_aligned_triplets.keys(), self.commonsense_violated_triplets.keys(), num_classes,
+                              num_relations, device)

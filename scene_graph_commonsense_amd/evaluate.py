@@ -5,8 +5,14 @@
 One process per GPU over RCCL; the pair loops are one fused call per minibatch (``pair_loop.evaluate_minibatch`` /
 ``evaluate_sgdet_minibatch``); the DETR decoder outputs go through the HIP object front-end (``object_frontend.DetrFrontEnd``:
 soft-max / top-k / class re-indexing / boxes / per-class NMS, and the SGCLS label matching).  Evaluation needs no collective;
-every rank writes its own ``test_results_<rank>.json`` as in the reference.  Out of scope here as in DESIGN.md: the LLM
-``prepare_cs`` pipeline and ``save_vis_results`` (they raise).
+every rank writes its own ``test_results_<rank>.json`` as in the reference.
+
+``run_mode prepare_cs`` (``evaluate.py:41-42,99-101,193-221``) runs here too: step 1 is the PredCLS pass with
+``Evaluator.get_related_top_k_predictions_parallel(top_k=10)`` in the place of ``compute()`` - ranking and the candidate scan on the
+device, the judged edge lists written per image - and step 2 walks the loader without a forward (the host dataset accumulates the
+triplets in ``__getitem__``) and ends with ``curr_dataset.save_all_triplets()``.  The LLM itself stays outside: the judge is
+``args['models']['cs_judge']`` or the host repository's ``query_llm``; this package opens no connection.  Out of scope as in
+DESIGN.md: ``save_vis_results`` (it raises).
 """
 from __future__ import annotations
 
@@ -30,7 +36,7 @@ def _loader(args, test_subset, rank, world_size):
                                        collate_fn=_host("collate_fn", _collate), num_workers=0, drop_last=True, sampler=sampler)
 
 
-def _start(gpu, args, test_subset):
+def _start(gpu, args, test_subset, with_model=True):
     rank = gpu
     world_size = int(os.environ.get("WORLD_SIZE", 0)) or max(torch.cuda.device_count(), 1)
     setup(rank, world_size)
@@ -39,6 +45,8 @@ def _start(gpu, args, test_subset):
     print("Finished loading the datasets...")
     with open(args["training"]["result_path"] + "test_results_" + str(rank) + ".json", "w") as f:
         json.dump([], f)
+    if not with_model:
+        return rank, loader, None, None
     model = build_classifier(args, rank)
     detr = build_feature_encoder(args, rank)
     model.eval()
@@ -56,14 +64,32 @@ def _finish(name):
 def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
     """Predicate classification (``evaluate.py:29-227``)."""
     T = args["training"]
-    if T["run_mode"] == "prepare_cs" or prepare_cs_step != -1:
-        raise NotImplementedError("the LLM commonsense collection (run_mode prepare_cs) is outside this package's scope (DESIGN.md)")
+    prepare_cs = T["run_mode"] == "prepare_cs"
+    if prepare_cs != (prepare_cs_step != -1) or (prepare_cs and prepare_cs_step not in (1, 2)):
+        raise ValueError("prepare_cs_step is 1 or 2 with run_mode prepare_cs and -1 otherwise (main.py:112-114)")
     if T.get("save_vis_results"):
         raise NotImplementedError("save_vis_results is outside this package's scope (DESIGN.md)")
+    if prepare_cs:
+        if curr_dataset is None:
+            raise ValueError("run_mode prepare_cs needs curr_dataset (the dataset behind test_subset: its train_cs_step selects the step)")
+        if args["dataset"]["dataset"] != "vg":
+            raise ValueError("run_mode prepare_cs is defined for Visual Genome only (evaluate.py:192-200)")
+        curr_dataset.train_cs_step = prepare_cs_step
+    if prepare_cs_step == 2:
+        # nothing to score: the host dataset's __getitem__ accumulates every image's triplets from the files of step 1
+        rank, loader, _, _ = _start(gpu, args, test_subset, with_model=False)
+        print("Start Testing PC...")
+        for _ in loader:
+            pass
+        curr_dataset.save_all_triplets()
+        _finish("PC")
+        return None, None
     rank, loader, model, detr = _start(gpu, args, test_subset)
     hier, vg = args["models"]["hierarchical_pred"], args["dataset"]["dataset"] == "vg"
     Recall = Evaluator(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100])
     Recall_top3 = Evaluator_Top3(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100]) if vg else None
+    if prepare_cs:
+        Recall_top3 = None                  # the mining reads Recall only; the reference's Top-3 result of this mode is never recorded
     record_test = _host("record_test_results", _record_test)
     test_record = []
     stats = torch.zeros(5, dtype=torch.int64, device=rank)
@@ -91,7 +117,12 @@ def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
             if model.last_connectivity_stats is not None:
                 stats += model.last_connectivity_stats
             if feed:
-                if vg:
+                if prepare_cs:
+                    # candidates mined from the state as accumulated: no connectivity term, no recall (evaluate.py:193-202)
+                    _, _, cache_hit_percentage = Recall.get_related_top_k_predictions_parallel(top_k=10)
+                    if last:
+                        print("cache hit percentage", cache_hit_percentage)
+                elif vg:
                     recall, _, mean_recall, recall_zs, _, mean_recall_zs = Recall.compute(per_class=True)
                     if hier:
                         recall_top3, _, mean_recall_top3 = Recall_top3.compute(per_class=True)
@@ -99,7 +130,7 @@ def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
                 else:
                     recall, _, mean_recall, _, _, _ = Recall.compute(per_class=True)
                     wmap_rel, wmap_phrase = Recall.compute_precision()
-                if batch_count % T["print_freq_test"] == 0 or last:
+                if not prepare_cs and (batch_count % T["print_freq_test"] == 0 or last):
                     s = stats.tolist()
                     record_test(args, test_record, rank, T["test_epoch"], recall_top3, recall, mean_recall_top3, mean_recall, recall_zs,
                                 mean_recall_zs, torch.tensor(float(s[4])), s[1], s[0], torch.tensor(float(s[3])), s[2], wmap_rel, wmap_phrase)

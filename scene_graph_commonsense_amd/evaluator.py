@@ -11,6 +11,10 @@ signatures and return tuples.  What changes underneath:
   continues past a label/box match whose predicate differs) is vectorised on the host instead of a triple Python
   loop of device scalar compares.  Grid IoU of two rasterised rectangles is their closed-form integer overlap.
 
+``get_related_top_k_predictions_parallel`` (``evaluator.py:375-462``, the candidate mining of ``run_mode prepare_cs``) ranks with the same
+kernel and scans the ranked candidates against the connected ground truth on the device (``sgc_related_topk``, one wavefront per
+image); the LLM verdict is a pluggable ``judge`` callable, by default the host repository's ``query_llm``.
+
 Reference quirks that are kept: ``confidence += connectivity`` mutates state inside ``compute``; hit/target
 counters persist across ``clear_data``; ``-inf`` candidates are not removed; ``Evaluator_Top3`` counts a hit for
 ``j < max(k, num_target)``.  There is no CPU ranking fallback: tensors must live on the GPU.
@@ -139,7 +143,62 @@ def recall_hits(cand, keep_pos, keep_cnt, targets, K, feature_size, iou_thresh, 
     return hit.cpu().numpy()
 
 
+def related_topk(cand, keep_pos, keep_cnt, top_k, targets, t_ptr):
+    """Device scan of the commonsense candidate mining (``sgc_related_topk``, reference ``evaluator.py:375-416``).  ``cand`` =
+    dict(scat, ocat, pred int64 [n]; sbox, obox [n,4]; conf f32 [n]), ``keep_pos`` [n_img,K] / ``keep_cnt`` [n_img] int32 the ranking,
+    ``targets`` = dict(scat, ocat int64 [t]; sbox, obox [t,4]) of the CONNECTED ground-truth triples grouped by image in accumulation
+    order, ``t_ptr`` [n_img+1] int32.  Returns device tensors (pos [n_img,16] int32 flat candidate positions, -1 padded; rank
+    [n_img,16] int32; count [n_img] int32; conf [n_img,16] f32, NaN padded); nothing synchronises with the host."""
+    lib = _lib.load()
+    dev = keep_pos.device
+    n_img, K = int(keep_pos.shape[0]), int(keep_pos.shape[1])
+    if not (1 <= int(top_k) <= K <= 128):
+        raise ValueError("top_k must satisfy 1 <= top_k <= K <= 128 (got top_k=%d, K=%d)" % (int(top_k), K))
+    i64 = lambda x: x.to(dev, torch.int64).contiguous()
+    f32 = lambda x: x.to(dev, torch.float32).contiguous().view(-1, 4)
+    c_s, c_o, c_p, c_sb, c_ob = i64(cand["scat"]), i64(cand["ocat"]), i64(cand["pred"]), f32(cand["sbox"]), f32(cand["obox"])
+    c_cf = cand["conf"].to(dev, torch.float32).contiguous()
+    t_s, t_o, t_sb, t_ob = i64(targets["scat"]), i64(targets["ocat"]), f32(targets["sbox"]), f32(targets["obox"])
+    pos = torch.empty(max(n_img, 1), 16, dtype=torch.int32, device=dev)
+    rank, conf = torch.empty_like(pos), torch.empty(max(n_img, 1), 16, dtype=torch.float32, device=dev)
+    count = torch.zeros(max(n_img, 1), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.sgc_related_topk(_lib.ptr(c_s), _lib.ptr(c_o), _lib.ptr(c_p), _lib.ptr(c_sb), _lib.ptr(c_ob), _lib.ptr(c_cf),
+                                        int(c_s.numel()), _lib.ptr(keep_pos.contiguous()), _lib.ptr(keep_cnt.contiguous()), K, int(top_k),
+                                        _lib.ptr(t_ptr.to(dev, torch.int32).contiguous()), _lib.ptr(t_s), _lib.ptr(t_o), _lib.ptr(t_sb),
+                                        _lib.ptr(t_ob), n_img, _lib.ptr(pos), _lib.ptr(rank), _lib.ptr(count), _lib.ptr(conf),
+                                        _lib.stream_ptr()), "sgc_related_topk")
+    return pos[:n_img], rank[:n_img], count[:n_img], conf[:n_img]
+
+
+def default_names():
+    """(object_names, relation_names) from the host repository's ``dataset_utils`` (``evaluator.py:451-452``), or None."""
+    try:
+        from dataset_utils import object_class_int2str, relation_by_super_class_int2str
+    except Exception:
+        return None
+    return object_class_int2str(), relation_by_super_class_int2str()
+
+
+def host_llm_judge(evaluator):
+    """The default judge of the commonsense mining: the host repository's ``query_llm.batch_query_openai_gpt`` for the text model,
+    with the host's ``EdgeCache`` kept on the evaluator (``evaluator.py:71,422``).  This package opens no connection itself."""
+    try:
+        from query_llm import EdgeCache, batch_query_openai_gpt
+    except Exception as e:
+        raise RuntimeError("no commonsense judge: pass judge=callable(predictions, context) -> list[int] (or set Evaluator.judge / "
+                           "args['models']['cs_judge']), or make the host repository's query_llm importable (%s)" % (e,))
+    if getattr(evaluator, "cache", None) is None:
+        evaluator.cache = EdgeCache(max_cache_size=evaluator.max_cache_size)
+
+    def judge(predictions, context):
+        return batch_query_openai_gpt(predictions, evaluator.cache, cache_hits=context["cache_hits"])
+    return judge
+
+
 class Evaluator:
+    names = None        # (object_names, relation_names) of the mined edge strings; None = the host repository's dataset_utils tables
+
     def __init__(self, args, num_classes, iou_thresh, top_k, max_cache_size=10000):
         self.args = args
         self.hierar = args["models"]["hierarchical_pred"]
@@ -183,6 +242,12 @@ class Evaluator:
             pv = d.get("commonsense_violated_triplets", "triplets/commonsense_violated_triplets%s.pt" % suffix)
             self._cs_keys = (list(torch.load(pa).keys()), list(torch.load(pv).keys()))
         self.annotation_paths = None
+        # commonsense candidate mining (run_mode prepare_cs, evaluator.py:67-74): judge(predictions, context), name tables, cache counters
+        self.judge = args["models"].get("cs_judge")
+        self.cache = None
+        self.max_cache_size = max_cache_size
+        self.cache_hits = 0
+        self.total_cache_queries = 0
         self._equiv = _equiv_matrix()
         self.last_topk = {}
         self.clear_data()
@@ -216,6 +281,10 @@ class Evaluator:
     object_bbox_pred = property(lambda s: s._cat("obox"))
     relation_target = property(lambda s: s._cat("rel_t") if s._targets_by_image is None else s._targets_by_image[0])
     which_in_batch_target = property(lambda s: s._cat("which_t"))
+    subject_cat_target = property(lambda s: s._cat("scat_t") if s._targets_by_image is None else s._targets_by_image[1])
+    object_cat_target = property(lambda s: s._cat("ocat_t") if s._targets_by_image is None else s._targets_by_image[2])
+    subject_bbox_target = property(lambda s: s._cat("sbox_t") if s._targets_by_image is None else s._targets_by_image[3])
+    object_bbox_target = property(lambda s: s._cat("obox_t") if s._targets_by_image is None else s._targets_by_image[4])
 
     # ------------------------------------------------------------------ accumulate
     def accumulate(self, which_in_batch, relation_pred, relation_target, super_relation_pred, connectivity,
@@ -385,6 +454,105 @@ class Evaluator:
             recall_k_per_class_zs = [self.result_per_class_zs[k] / self.num_conn_target_per_class_zs for k in self.top_k]
             mean_recall_k_zs = [torch.nanmean(r) for r in recall_k_per_class_zs]
         return recall_k, recall_k_per_class, mean_recall_k, recall_k_zs, recall_k_per_class_zs, mean_recall_k_zs
+
+    # ------------------------------------------------------------------ commonsense candidate mining (prepare_cs)
+    def related_top_k_device(self, top_k):
+        """Ranking + scan of ``get_related_top_k_predictions_parallel`` on the device: (images [n_img] sorted, pos, rank, count, conf)
+        as ``related_topk`` returns them, over the state as it stands (``confidence`` WITHOUT the connectivity term when called
+        instead of ``compute()``, as ``evaluate.py:200`` does).  PredCLS state only."""
+        if self._targets_by_image is not None:
+            raise ValueError("the commonsense candidate mining covers PredCLS state only (targets fed through accumulate, not accumulate_target)")
+        if not (1 <= int(top_k) <= 128):
+            raise ValueError("top_k must be in 1..128 (sgc_topk_per_image ranks at most 128 candidates per image)")
+        conf, which = self._cat("conf"), self._cat("which")
+        images, keep_pos, keep_cnt, _, _, _ = rank_topk_device(conf, which, int(top_k))
+        dev = conf.device
+        rel_all = self._cat("rel_t")
+        if rel_all is None:
+            sel = torch.zeros(0, dtype=torch.int64, device=dev)
+            row = sel
+        else:
+            sel = torch.nonzero(rel_all != -1).flatten()
+            wt = self._cat("which_t")[sel]
+            row = torch.searchsorted(images, wt)
+            known = images[row.clamp(max=len(images) - 1)] == wt          # targets of images without any candidate are not scanned
+            sel, row = sel[known], row[known]
+            by_image = torch.sort(row, stable=True)[1]                     # grouped by image, accumulation order kept
+            sel, row = sel[by_image], row[by_image]
+        t_ptr = torch.zeros(len(images) + 1, dtype=torch.int32, device=dev)
+        if int(sel.numel()) > 0:
+            t_ptr[1:] = torch.cumsum(torch.bincount(row, minlength=len(images)), 0).int()
+            tg = dict(scat=self._cat("scat_t")[sel], ocat=self._cat("ocat_t")[sel], sbox=self._cat("sbox_t")[sel], obox=self._cat("obox_t")[sel])
+        else:
+            z = torch.zeros(0, dtype=torch.int64, device=dev)
+            tg = dict(scat=z, ocat=z, sbox=torch.zeros(0, 4, device=dev), obox=torch.zeros(0, 4, device=dev))
+        cand = dict(scat=self._cat("scat"), ocat=self._cat("ocat"), pred=self._cat("pred"), sbox=self._cat("sbox"), obox=self._cat("obox"),
+                    conf=conf)
+        return (images,) + related_topk(cand, keep_pos, keep_cnt, int(top_k), tg, t_ptr)
+
+    def get_related_top_k_predictions_parallel(self, top_k, save_to_annot=True, judge=None, names=None):
+        """Commonsense candidate mining of ``run_mode prepare_cs`` (``evaluator.py:375-462``): per image (rows in sorted unique image
+        order) the ranked candidates among the first ``top_k`` that share a subject or an object (class AND box, by value) with a
+        connected ground-truth triple, de-duplicated on the triple, with the reference's `>= 10` cut as written (``sgc_related_topk``;
+        ranking ``sgc_topk_per_image``, ties in append order).  Every image's strings go to the judge -
+        ``judge(predictions: list[str], context: dict) -> list[int]`` or ``-> (list[int], cache_hits)``, 1 = commonsense-aligned;
+        ``context`` holds ``image``, ``annot_name``, ``top_k``, ``llm_model``, ``cache_hits`` (the running count the second form returns
+        updated), ``sub_bbox`` / ``obj_bbox`` (the image's candidate boxes) and ``image_dir``.  The judge is the argument, else
+        ``self.judge`` (``args['models']['cs_judge']``), else the host repository's ``query_llm.batch_query_openai_gpt`` for the text
+        model.  The aligned and the violated edge lists of every image with at least one edge are written with ``torch.save`` to the
+        reference's paths under ``args['dataset']['annot_dir']`` (``evaluator.py:436-444``).  Returns, with ``save_to_annot``,
+        (top_k_predictions, top_k_image_graphs, cache_hit_percentage); an edge is [subject_bbox, relation_id, object_bbox, confidence, j].
+        ``names`` = (object_names, relation_names), else ``self.names``, else the host repository's ``dataset_utils`` tables."""
+        names = names if names is not None else (self.names if self.names is not None else default_names())
+        if names is None:
+            raise RuntimeError("the edge strings need the class names: pass names=(object_names, relation_names), set Evaluator.names, "
+                               "or make the host repository's dataset_utils importable")
+        gpt4v = self.args["models"].get("llm_model") == "gpt4v"
+        judge = judge if judge is not None else self.judge
+        if judge is None:
+            if gpt4v:
+                raise RuntimeError("llm_model gpt4v needs a custom judge: pass judge=callable(predictions, context) (the image query is "
+                                   "not wrapped by this package)")
+            judge = host_llm_judge(self)
+        top_k_predictions, top_k_image_graphs = [], []
+        if self._cat("conf") is not None:
+            images, pos, rank, count, econf = self.related_top_k_device(top_k)
+            safe = pos.clamp(min=0).long()
+            fields = [self._cat(k)[safe] for k in ("scat", "pred", "ocat", "sbox", "obox")]
+            images_h, count_h, rank_h, conf_h = images.tolist(), count.tolist(), rank.tolist(), econf.cpu()
+            scat_h, pred_h, ocat_h, sbox_h, obox_h = [f.cpu() for f in fields]
+            which = self._cat("which")
+            suffix = "_gpt4v" if gpt4v else "_gpt3p5_temp"
+            for r, image in enumerate(images_h):
+                n = count_h[r]
+                preds = [names[0][int(scat_h[r, e])] + " " + names[1][int(pred_h[r, e])] + " " + names[0][int(ocat_h[r, e])] for e in range(n)]
+                graph = [[sbox_h[r, e].tolist(), int(pred_h[r, e]), obox_h[r, e].tolist(), conf_h[r, e].item(), rank_h[r][e]] for e in range(n)]
+                top_k_predictions.append(preds)
+                top_k_image_graphs.append(graph)
+                if n == 0:
+                    continue
+                annot = self.annotation_paths[image]
+                context = dict(image=image, annot_name=annot, top_k=int(top_k), llm_model=self.args["models"].get("llm_model"),
+                               cache_hits=self.cache_hits, image_dir=self.args["dataset"].get("image_dir"))
+                if gpt4v:
+                    cur = which == image
+                    context.update(sub_bbox=self._cat("sbox")[cur], obj_bbox=self._cat("obox")[cur])
+                responses = judge(preds, context)
+                if isinstance(responses, tuple):
+                    responses, self.cache_hits = responses
+                if len(responses) != n:
+                    raise ValueError("the judge returned %d responses for %d predictions" % (len(responses), n))
+                self.total_cache_queries += n
+                valid = [graph[e] for e in range(n) if responses[e] == 1]
+                invalid = [graph[e] for e in range(n) if responses[e] != 1]
+                annot_name = annot[:-16] + "_pseudo_annotations.pkl"
+                for kind, edges in (("cs_aligned_top", valid), ("cs_violated_top", invalid)):
+                    path = os.path.join(self.args["dataset"]["annot_dir"], kind + str(top_k) + suffix, annot_name)
+                    os.makedirs(os.path.dirname(path), exist_ok=True)
+                    torch.save(edges, path)
+        cache_hit_percentage = (self.cache_hits / self.total_cache_queries) * 100 if self.total_cache_queries > 0 else 0
+        if save_to_annot:
+            return top_k_predictions, top_k_image_graphs, cache_hit_percentage
 
     def compute_precision(self):
         """OpenImages weighted mean AP over the top-20 predictions per image (``evaluator.py:522-566``)."""

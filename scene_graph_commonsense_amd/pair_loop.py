@@ -418,6 +418,68 @@ def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool 
     return attach_objects(graphs, scene.cats, raw, cfg.feature_size)
 
 
+def mine_commonsense_candidates(model, batch, top_k: int = 10, overlap_filtering: bool = True, scene: Optional[DeviceScene] = None,
+                                workspace_budget: Optional[float] = None):
+    """The candidate mining of ``run_mode prepare_cs`` for one minibatch without an ``Evaluator`` (``scene_graph.MinedCandidates``,
+    device tensors; ``.to_lists(names)`` gives the lists of ``Evaluator.get_related_top_k_predictions_parallel``, and equals them
+    exactly: both rank the same forward outputs).  The forward's candidates are ranked in place by ``sgc_scene_graph_topk`` - no
+    connectivity term (``evaluate.py:200`` mines instead of ``compute()``), the overlap mask and the kept steps of
+    ``predict_scene_graphs`` - and the ranked fields go straight to ``sgc_related_topk`` with the connected targets of the kept steps,
+    per image in pair order (what ``feed_evaluators`` appends).  ``batch`` needs relation targets.  No appended int64 copies, and
+    nothing after the forward synchronises with the host."""
+    from .evaluator import related_topk
+    from .scene_graph import MinedCandidates, rank_scene_graphs
+    cfg = model.head_config()
+    dev = next(model.parameters()).device
+    if scene is None:
+        scene = flatten_scene(cfg, batch, dev)
+    directed = scene.directed
+    if directed is None:
+        if getattr(batch, "relationships", None) is None:
+            raise ValueError("the candidate mining needs relation targets: a batch with relationships / subj_or_obj")
+        directed = torch.from_numpy(pair_targets_fast(batch.relationships, batch.subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
+    ptr, lst = image_pair_lists(scene)
+    raw = getattr(scene, "_bbox_raw_d", None)
+    if raw is None:
+        raw = scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(dev)
+    iou = overlap_mask(scene) if overlap_filtering else None
+    included = _step_filter(scene, iou)[0] if overlap_filtering else None
+    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
+    if len(groups) > 1:
+        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, None)
+    else:
+        out = model.forward_pairs(scene, iou_mask=iou)
+    model.last_image_groups, model.last_outputs = groups, out
+    P, B, K = scene.n_pairs, int(ptr.numel()) - 1, int(top_k)
+    g = rank_scene_graphs(out.cand_conf, out.cand_pred, torch.zeros(P, device=dev), ptr, top_k=K, pair_list=lst, slot_major=False,
+                          mask=iou, included=included, sub_idx=scene.sub_idx, obj_idx=scene.obj_idx, cats=scene.cats)   # x + 0 is exact
+    # the ranked [B,K] fields ARE the flat candidate arrays of the scan: candidate b*K + j is rank j of image b
+    ranked = g.subject >= 0
+    sub, obj = g.subject.clamp(min=0).long().reshape(-1), g.object.clamp(min=0).long().reshape(-1)
+    if int(scene.cats.numel()) == 0:
+        return MinedCandidates(*[torch.full((B, 16), -1, dtype=torch.int32, device=dev) for _ in range(6)],
+                               torch.full((B, 16), float("nan"), device=dev), torch.zeros(B, dtype=torch.int32, device=dev), g.count,
+                               scene.cats, raw)
+    cand = dict(scat=scene.cats[sub], ocat=scene.cats[obj], pred=g.predicate.reshape(-1), sbox=raw[sub], obox=raw[obj], conf=g.score.reshape(-1))
+    keep_pos = torch.where(ranked, torch.arange(B * K, dtype=torch.int32, device=dev).view(B, K), torch.full_like(g.subject, -1))
+    # connected targets of the kept steps, per image in pair order, compacted without a host synchronisation
+    rows = lst.long()
+    flag = directed.to(dev)[rows] != -1
+    if included is not None:
+        flag &= included[rows].bool()
+    incl = torch.cumsum(flag.int(), 0)
+    t_ptr = torch.cat((torch.zeros(1, dtype=incl.dtype, device=dev), incl))[ptr.long()].int()
+    dest = torch.where(flag, incl.long() - 1, torch.full_like(rows, P))                 # row P: the slot the others are dropped into
+    t_sub, t_obj = scene.sub_idx.long()[rows], scene.obj_idx.long()[rows]
+    compact = lambda v: torch.zeros((P + 1,) + tuple(v.shape[1:]), dtype=v.dtype, device=dev).index_put_((dest,), v)[:P]
+    tg = dict(scat=compact(scene.cats[t_sub]), ocat=compact(scene.cats[t_obj]), sbox=compact(raw[t_sub].float()), obox=compact(raw[t_obj].float()))
+    pos, rank, count, score = related_topk(cand, keep_pos.contiguous(), g.count, K, tg, t_ptr)
+    at = rank.clamp(min=0).long()
+    pick = lambda t: torch.where(rank >= 0, t.gather(1, at), torch.full_like(rank, -1))
+    return MinedCandidates(pick(g.pair), pick(g.slot), pick(g.predicate), pick(g.subject), pick(g.object), rank, score, count, g.count,
+                           scene.cats, raw)
+
+
 def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[DeviceScene] = None,
                     workspace_budget: Optional[float] = None, streams: Optional[int] = None, input_grads: bool = False, **loss_kw):
     """One optimisation step over all ordered pairs of the minibatch; returns the loss tensor.

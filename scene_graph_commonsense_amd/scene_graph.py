@@ -71,6 +71,52 @@ class SceneGraphs:
         return out
 
 
+@dataclass
+class MinedCandidates:
+    """Commonsense candidates of B images (``pair_loop.mine_commonsense_candidates``): per image up to 11 ranked candidates that share
+    an endpoint with a connected ground-truth triple, in acceptance order (reference ``evaluator.py:375-416``).  Device tensors; slots
+    past ``count`` hold -1 / NaN."""
+    pair: torch.Tensor            # [B,16] int32  pair row of the minibatch
+    slot: torch.Tensor            # [B,16] int32  super-category slot of the candidate
+    predicate: torch.Tensor       # [B,16] int32
+    subject: torch.Tensor         # [B,16] int32  flattened object index
+    object: torch.Tensor          # [B,16] int32
+    rank: torch.Tensor            # [B,16] int32  the rank j of the candidate among the image's candidates
+    score: torch.Tensor           # [B,16] f32    the candidate's confidence (no connectivity term)
+    count: torch.Tensor           # [B] int32
+    n_candidates: Optional[torch.Tensor] = None    # [B] int32  min(top_k, candidates of the image)
+    cats: Optional[torch.Tensor] = None            # [n_obj] int64 object classes of the minibatch
+    boxes: Optional[torch.Tensor] = None           # [n_obj,4] raw grid boxes (x0,x1,y0,y1) as given
+
+    def to_lists(self, names, cats=None, boxes=None, all_images=False):
+        """(top_k_predictions, top_k_image_graphs) as ``Evaluator.get_related_top_k_predictions_parallel`` returns them: per image the
+        strings "subject predicate object" (``names`` = (object_names, relation_names)) and the edges [subject_bbox, relation_id,
+        object_bbox, confidence, j].  Rows are the images that have at least one candidate, in order - the evaluator's sorted unique
+        images - or, with ``all_images``, all B images.  ``cats`` / ``boxes``: per-object tables, default the minibatch's own.  The
+        first host synchronisation of the route."""
+        cats = self.cats if cats is None else cats
+        boxes = self.boxes if boxes is None else boxes
+        if cats is None or boxes is None:
+            raise ValueError("to_lists needs the per-object cats and boxes")
+        host = lambda t: torch.as_tensor(t).detach().cpu()
+        cats, boxes = host(cats), host(boxes)
+        count, pred, sub, obj = host(self.count).tolist(), host(self.predicate), host(self.subject), host(self.object)
+        rank, score = host(self.rank).tolist(), host(self.score)
+        has = [True] * len(count) if (all_images or self.n_candidates is None) else [n > 0 for n in host(self.n_candidates).tolist()]
+        preds, graphs = [], []
+        for b, n in enumerate(count):
+            if not has[b]:
+                continue
+            p, g = [], []
+            for e in range(n):
+                s, o, r = int(sub[b, e]), int(obj[b, e]), int(pred[b, e])
+                p.append(names[0][int(cats[s])] + " " + names[1][r] + " " + names[0][int(cats[o])])
+                g.append([boxes[s].tolist(), r, boxes[o].tolist(), score[b, e].item(), rank[b][e]])
+            preds.append(p)
+            graphs.append(g)
+        return preds, graphs
+
+
 def _as(t, dtype, n, what):
     if t is None:
         return None
