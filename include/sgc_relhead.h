@@ -411,6 +411,37 @@ int sgc_related_topk(const long* c_scat, const long* c_ocat, const long* c_pred,
                      const long* t_scat, const long* t_ocat, const float* t_sbox, const float* t_obox, int n_img, int* out_pos,
                      int* out_rank, int* out_count, float* out_conf, void* stream);
 
+/* Recall@K counters on the device (evaluator.py:306-367; Evaluator_Top3 :720-773 with n_pred = 3), updated from the ranked lists of
+ * sgc_scene_graph_topk (out_pair / out_pred / out_sub / out_obj [n_img][K], out_count [n_img], 1 <= K <= 128; out_pair is read with
+ * n_pred = 3 only) and the scene's tables: cats [n_obj] int64, boxes [n_obj][4] f32 raw (x0,x1,y0,y1), 16-byte aligned (int()
+ * truncation and slice clipping applied inside), sub_idx / obj_idx / image / directed [n_pairs] int32, included u8 [n_pairs] or NULL.
+ * One wavefront per pair row; a row is a target when directed != -1 and included != 0, its labels and boxes are cats / boxes of
+ * sub_idx / obj_idx, a ranked candidate's those of out_sub / out_obj.  Hit rank = sgc_recall_hits' scan (labels equal, both grid
+ * IoUs >= iou_thresh, predicate equal - with n_pred = 3 any of cand_pred[out_pair][0..2], cand_pred [n_pairs][3] int32; -inf
+ * candidates take part).  For every k of top_k (HOST array, n_k <= 8) the hit counts when hit < k and hit < out_count; with
+ * n_pred = 3 when hit < out_count and hit < max(k, img_targets[image]), img_targets [n_img] int32 = the image's number of targets.
+ * int64 counters, added to with integer atomics (the sums are order-independent): hits [n_k], hits_pc [n_k][R], targets [1],
+ * targets_pc [R], and their zero-shot twins for targets whose bit (s*R + r)*C + o is set in zero_shot (sgc_commonsense_filter's
+ * bitmap layout; NULL = none, the twins may then be NULL). */
+int sgc_recall_accumulate(const int* out_pair, const int* out_pred, const int* out_sub, const int* out_obj, const int* out_count,
+                          int n_img, int K, const int* cand_pred, int n_pred, const long* cats, const float* boxes, int n_obj,
+                          const int* sub_idx, const int* obj_idx, const int* image, const int* directed,
+                          const unsigned char* included, int n_pairs, const int* img_targets, const int* top_k, int n_k,
+                          const unsigned* zero_shot, int C, int R, int feature_size, double iou_thresh, long* hits, long* hits_pc,
+                          long* targets, long* targets_pc, long* zs_hits, long* zs_hits_pc, long* zs_targets, long* zs_targets_pc,
+                          void* stream);
+
+/* OpenImages precision counters on the device (evaluator.py:522-557): one wavefront per (image, rank j < min(n_rank, out_count)) of
+ * the same ranked lists; image_ptr [n_img+1] / pair_list: the pair rows of every image (pair_list NULL = the rows image_ptr[b] ..
+ * image_ptr[b+1]-1).  Over the image's targets (directed != -1, included != 0) with the candidate's labels and predicate:
+ * found = some target has both grid IoUs >= iou_thresh, found_union = some target's (subject | object) mask has IoU >= iou_thresh
+ * with the candidate's (evaluator.py:97-115; exact cell counts, union == 0 -> 0).  num_ap[pred] += 1, ap[pred] += found,
+ * ap_union[pred] += found_union; int64 [R] each. */
+int sgc_precision_accumulate(const int* out_pred, const int* out_sub, const int* out_obj, const int* out_count, int n_img, int K,
+                             int n_rank, const int* image_ptr, const int* pair_list, const long* cats, const float* boxes, int n_obj,
+                             const int* sub_idx, const int* obj_idx, const int* directed, const unsigned char* included, int n_pairs,
+                             int R, int feature_size, double iou_thresh, long* ap, long* ap_union, long* num_ap, void* stream);
+
 /* "iou_mask" of testing(): the two boxes overlap on the FxF grid   (train_test.py:403-408).  bbox [n_obj][4], out u8 [n_pairs]. */
 int sgc_overlap_filter(const int* bbox, const int* sub_idx, const int* obj_idx, unsigned char* out, int n_pairs, void* stream);
 

@@ -24,7 +24,8 @@ import torch.distributed as dist
 
 from .evaluator import Evaluator, Evaluator_Top3
 from .object_frontend import DetrFrontEnd
-from .pair_loop import MinibatchLookahead, evaluate_minibatch, evaluate_sgdet_minibatch, freeze_setup_objects
+from .metrics import RecallMeter
+from .pair_loop import MinibatchLookahead, evaluate_minibatch, evaluate_sgdet_minibatch, freeze_setup_objects, score_minibatch
 from .pairs import flatten_scene
 from .train_test import (_collate, _host, _record_test, _to_batch, build_classifier, build_feature_encoder, load_checkpoint, setup)
 from .train_utils import process_image_features
@@ -61,8 +62,22 @@ def _finish(name):
     print("FINISHED TESTING %s\n" % name)
 
 
+def _meter_results(meter, vg, hier):
+    """The record's numbers from a ``RecallMeter`` - its only host reads: (recall, mean_recall, recall_top3, mean_recall_top3, recall_zs,
+    mean_recall_zs, wmap_rel, wmap_phrase), None where the evaluator route leaves None."""
+    recall, _, mean_recall, recall_zs, _, mean_recall_zs = meter.compute(per_class=True)
+    recall_top3 = mean_recall_top3 = wmap_rel = wmap_phrase = None
+    if vg and hier:
+        recall_top3, _, mean_recall_top3 = meter.compute_top3(per_class=True)
+    if not vg:
+        wmap_rel, wmap_phrase = meter.compute_precision()
+    return recall, mean_recall, recall_top3, mean_recall_top3, recall_zs, mean_recall_zs, wmap_rel, wmap_phrase
+
+
 def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
-    """Predicate classification (``evaluate.py:29-227``)."""
+    """Predicate classification (``evaluate.py:29-227``).  With ``args['training']['device_metrics']`` (not in ``prepare_cs``) the two
+    evaluators are replaced by one ``metrics.RecallMeter``: ``pair_loop.score_minibatch`` updates its device counters per minibatch
+    and the host reads them only where a record is written; the records are the same."""
     T = args["training"]
     prepare_cs = T["run_mode"] == "prepare_cs"
     if prepare_cs != (prepare_cs_step != -1) or (prepare_cs and prepare_cs_step not in (1, 2)):
@@ -86,10 +101,6 @@ def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
         return None, None
     rank, loader, model, detr = _start(gpu, args, test_subset)
     hier, vg = args["models"]["hierarchical_pred"], args["dataset"]["dataset"] == "vg"
-    Recall = Evaluator(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100])
-    Recall_top3 = Evaluator_Top3(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100]) if vg else None
-    if prepare_cs:
-        Recall_top3 = None                  # the mining reads Recall only; the reference's Top-3 result of this mode is never recorded
     record_test = _host("record_test_results", _record_test)
     test_record = []
     stats = torch.zeros(5, dtype=torch.int64, device=rank)
@@ -106,6 +117,31 @@ def eval_pc(gpu, args, test_subset, curr_dataset=None, prepare_cs_step=-1):
         except (ValueError, IndexError):
             return None
         return batch, annot_path, flatten_scene(cfg, batch, dev)
+    if T.get("device_metrics") and not prepare_cs:
+        meter = RecallMeter(args, args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100], device=dev)
+        with torch.no_grad():
+            ahead = MinibatchLookahead(loader, prepare)
+            for batch_count, (batch, annot_path, scene) in ahead:
+                last = batch_count + 1 == len(loader)
+                feed = batch_count % T["eval_freq_test"] == 0 or last
+                if feed:
+                    score_minibatch(model, batch, meter, skip_filtered=skip, scene=scene)
+                else:
+                    evaluate_minibatch(model, batch, None, None, skip_filtered=skip, scene=scene)
+                if model.last_connectivity_stats is not None:
+                    stats += model.last_connectivity_stats
+                if feed and (batch_count % T["print_freq_test"] == 0 or last):
+                    recall, mean_recall, recall_top3, mean_recall_top3, recall_zs, mean_recall_zs, wmap_rel, wmap_phrase = \
+                        _meter_results(meter, vg, hier)
+                    s = stats.tolist()
+                    record_test(args, test_record, rank, T["test_epoch"], recall_top3, recall, mean_recall_top3, mean_recall, recall_zs,
+                                mean_recall_zs, torch.tensor(float(s[4])), s[1], s[0], torch.tensor(float(s[3])), s[2], wmap_rel, wmap_phrase)
+        _finish("PC")
+        return recall, mean_recall
+    Recall = Evaluator(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100])
+    Recall_top3 = Evaluator_Top3(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100]) if vg else None
+    if prepare_cs:
+        Recall_top3 = None                  # the mining reads Recall only; the reference's Top-3 result of this mode is never recorded
     with torch.no_grad():
         ahead = MinibatchLookahead(loader, prepare)
         for batch_count, (batch, annot_path, scene) in ahead:

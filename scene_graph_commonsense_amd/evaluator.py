@@ -37,6 +37,10 @@ _EQUIV = [[1, 5, 11, 23, 38, 44, 121, 124, 148, 149], [0, 50], [92, 137]]
 _UNSYMM = {123: [14, 63, 95, 87, 123], 108: [89, 102, 67, 72, 71, 81, 96, 105, 90, 111, 108],
            60: [145, 106, 142, 144, 77, 60]}
 
+# OpenImages predicate counts weighting the mean AP (reference utils.py:270-274; data); shared with metrics.RecallMeter
+OIV6_PREDICATE_WEIGHT = [1974, 120, 27, 2, 284, 571, 2059, 8, 26, 2, 0, 163, 25, 30, 2, 0, 0, 1, 0, 17, 0, 29, 14, 4,
+                         3, 0, 6, 0, 67, 5]
+
 
 def _equiv_matrix(n: int = 160) -> np.ndarray:
     m = np.eye(n, dtype=bool)
@@ -580,8 +584,7 @@ class Evaluator:
                     if np.any(ok & (u_iou >= self.iou_thresh)):
                         self.result_per_class_ap_union[pj] += 1.0
                 self.num_conn_target_per_class_ap[pj] += 1.0
-        weight = torch.tensor([1974, 120, 27, 2, 284, 571, 2059, 8, 26, 2, 0, 163, 25, 30, 2, 0, 0, 1, 0, 17, 0, 29, 14, 4,
-                               3, 0, 6, 0, 67, 5]) + 1        # reference utils.py:270-274 (data)
+        weight = torch.tensor(OIV6_PREDICATE_WEIGHT) + 1
         ppc = self.result_per_class_ap / self.num_conn_target_per_class_ap
         not_nan = torch.logical_not(torch.isnan(ppc))
         wmp = torch.nansum(ppc * weight) / torch.sum(weight[not_nan])

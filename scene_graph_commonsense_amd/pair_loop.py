@@ -418,6 +418,51 @@ def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool 
     return attach_objects(graphs, scene.cats, raw, cfg.feature_size)
 
 
+def score_minibatch(model, batch, meter, overlap_filtering: bool = True, scene: Optional[DeviceScene] = None, skip_filtered: bool = False,
+                    workspace_budget: Optional[float] = None, commonsense=None):
+    """``evaluate_minibatch`` for a ``metrics.RecallMeter`` instead of the two evaluators: the fused forward, then the meter's counters
+    (Recall@K, zero-shot recall, Top-3 for a hierarchical Visual Genome head, the OpenImages precision counters) updated on the device
+    from the forward's outputs and the scene's tables - the candidates, filters and tie order of ``evaluate_minibatch`` +
+    ``Evaluator.compute()`` + ``Evaluator_Top3.compute()`` / ``compute_precision()``, without the appended int64 copies and without a
+    read-back.  ``batch`` needs relation targets.  ``skip_filtered`` / ``workspace_budget`` as ``evaluate_minibatch``; ``commonsense``
+    as ``predict_scene_graphs`` (default: the meter's own sets in run mode eval_cs).  Sets ``model.last_outputs`` and, when the scene has
+    raw targets and nothing was skipped, ``model.last_connectivity_stats``.  Everything the update needs besides the forward's outputs
+    is put on the device BEFORE the forward is enqueued; nothing after it synchronises with the host - the numbers are the caller's
+    ``meter.compute*()``.  PredCLS only: SGDET / SGCLS stay on ``evaluate_sgdet_minibatch`` and the ``Evaluator``.
+    Returns (scene, outputs)."""
+    from .commonsense import TripletBitmaps
+    from .metrics import scene_boxes
+    cfg = model.head_config()
+    dev = next(model.parameters()).device
+    if scene is None:
+        scene = flatten_scene(cfg, batch, dev)
+    directed = scene.directed
+    if directed is None:
+        if getattr(batch, "relationships", None) is None:
+            raise ValueError("the metrics need relation targets: a batch with relationships / subj_or_obj")
+        directed = torch.from_numpy(pair_targets_fast(batch.relationships, batch.subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
+    image_pair_lists(scene)                         # the two per-scene tables of the update, made (and uploaded) once, before the forward
+    scene_boxes(scene, dev)
+    bitmaps = commonsense
+    if commonsense is not None and not isinstance(commonsense, TripletBitmaps):
+        bitmaps = model._commonsense_bitmaps(commonsense, dev)
+    iou = overlap_mask(scene) if overlap_filtering else None
+    included = _step_filter(scene, iou)[0] if overlap_filtering else None
+    select = _unfiltered_selection(scene, iou, (meter,)) if (skip_filtered and overlap_filtering) else None
+    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
+    if len(groups) > 1:
+        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
+    else:
+        out = model.forward_pairs(scene, iou_mask=iou, select=select)
+    model.last_image_groups, model.last_outputs = groups, out
+    meter.update(scene, out, overlap=iou, included=included, commonsense=bitmaps, top3=cfg.dataset == "vg", directed=directed)
+    model.last_connectivity_stats = None
+    if select is None and scene.raw_target is not None:
+        model.last_connectivity_stats = model.engine().connectivity_stats(
+            out.connectivity, directed, scene.raw_target, None if included is None else included.to(torch.uint8))
+    return scene, out
+
+
 def mine_commonsense_candidates(model, batch, top_k: int = 10, overlap_filtering: bool = True, scene: Optional[DeviceScene] = None,
                                 workspace_budget: Optional[float] = None):
     """The candidate mining of ``run_mode prepare_cs`` for one minibatch without an ``Evaluator`` (``scene_graph.MinedCandidates``,
