@@ -26,6 +26,7 @@ class TripletBitmaps:
         self.violated = self._pack(violated_keys)
 
     def _pack(self, keys) -> torch.Tensor:
+        # the layout that triplet_bits / triplet_bit read on the device (csrc/eval_geom.h): triplet (s, r, o) is bit (s*R + r)*C + o
         nbits = self.C * self.R * self.C
         nwords = (nbits + 31) // 32
         bits = np.zeros(nwords * 32, dtype=np.uint64)

@@ -1,5 +1,7 @@
 // Evaluation-side kernels: overlap filter (K10) and per-image stable top-K ranking (K9).
 #include "common.h"
+#include "eval_geom.h"
+#include "rank_select.h"
 
 // iou_mask of testing(): reference train_test.py:403-408 computes sum(mask_g | mask_e) / sum(mask_g & mask_e),
 // maps inf -> 0 and keeps ratio > 0, i.e. "the two rectangles share at least one grid cell"
@@ -16,114 +18,29 @@ __global__ void overlap_filter_kernel(const int* __restrict__ bbox, const int* _
     out[i] = (a_ok && b_ok && w > 0 && h > 0) ? 1 : 0;
 }
 
-__device__ __forceinline__ unsigned order_key(float f) {      // ascending uint order == ascending float order
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// One workgroup per image: radix-select the K-th largest confidence (4 x 8-bit LDS histograms), gather everything
-// above it plus the earliest ties (ordered compaction with wavefront ballots), bitonic-sort the <=128 survivors
-// by (confidence desc, index asc).  Equivalent to a stable descending argsort truncated to K
-// (reference evaluator.py:304,315-316 uses an unstable argsort; ties are resolved by append order here).
+// One workgroup per image: block_topk (csrc/rank_select.h) over the image's confidences.  Equivalent to a stable descending
+// argsort truncated to K (reference evaluator.py:304,315-316 uses an unstable argsort; ties are resolved by append order here).
 __global__ __launch_bounds__(256) void topk_kernel(const float* __restrict__ conf, const int* __restrict__ seg_ptr, int K,
                                                    int* __restrict__ out_idx, int* __restrict__ out_count) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_prefix, s_mask;
-    __shared__ int s_remaining, s_cnt, s_base, wave_cnt[4];
-    __shared__ unsigned long long keys[128];
-    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    __shared__ TopkScratch<256> sel;
+    const int img = blockIdx.x, tid = threadIdx.x;
     const int b = seg_ptr[img], n = seg_ptr[img + 1] - b;
     const int k = min(K, n);
     const float* c = conf + b;
-    if (tid < 128) keys[tid] = ~0ull;
-    if (tid == 0) { s_prefix = 0; s_mask = 0; s_remaining = k; s_cnt = 0; out_count[img] = k; }
-    __syncthreads();
-    if (k > 0) {
-        for (int pass = 3; pass >= 0; --pass) {
-            hist[tid] = 0;
-            __syncthreads();
-            const unsigned prefix = s_prefix, mask = s_mask;
-            for (int i = tid; i < n; i += 256) {
-                const unsigned key = order_key(c[i]);
-                if ((key & mask) == prefix) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int cum = 0, rem = s_remaining;
-                for (int bk = 255; bk >= 0; --bk) {
-                    const int hv = (int)hist[bk];
-                    if (cum + hv >= rem) {
-                        s_prefix = prefix | ((unsigned)bk << (8 * pass));
-                        s_mask = mask | (0xffu << (8 * pass));
-                        s_remaining = rem - cum;
-                        break;
-                    }
-                    cum += hv;
-                }
-            }
-            __syncthreads();
-        }
-        const unsigned thr = s_prefix;
-        for (int i = tid; i < n; i += 256) {
-            const unsigned key = order_key(c[i]);
-            if (key > thr) {
-                const int pos = atomicAdd(&s_cnt, 1);
-                keys[pos] = ((unsigned long long)(~key) << 32) | (unsigned)i;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) s_base = s_cnt;
-        __syncthreads();
-        for (int c0 = 0; c0 < n; c0 += 256) {
-            if (s_base >= k) break;
-            const int i = c0 + tid;
-            const bool flag = i < n && order_key(c[i]) == thr;
-            const unsigned long long bal = __ballot(flag);
-            const int within = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_cnt[wv] = __popcll(bal);
-            __syncthreads();
-            int off = s_base + within;
-            for (int w2 = 0; w2 < wv; ++w2) off += wave_cnt[w2];
-            if (flag && off < k) keys[off] = ((unsigned long long)(~thr) << 32) | (unsigned)i;
-            __syncthreads();
-            if (tid == 0) s_base += wave_cnt[0] + wave_cnt[1] + wave_cnt[2] + wave_cnt[3];
-            __syncthreads();
-        }
-        // bitonic sort of 128 keys, ascending ( = confidence descending, index ascending)
-        for (int size = 2; size <= 128; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                __syncthreads();
-                if (tid < 64) {
-                    const int lo = 2 * tid - (tid & (stride - 1));
-                    const int hi = lo + stride;
-                    const bool up = ((lo & size) == 0);
-                    const unsigned long long a = keys[lo], bb = keys[hi];
-                    if ((a > bb) == up) { keys[lo] = bb; keys[hi] = a; }
-                }
-            }
-        }
-        __syncthreads();
-    }
-    for (int j = tid; j < K; j += 256) out_idx[(long)img * K + j] = (j < k) ? (int)(keys[j] & 0xffffffffull) : -1;
+    if (tid == 0) out_count[img] = k;
+    block_topk<256>(sel, n, k, [&](int i) { return order_key(c[i]); });
+    for (int j = tid; j < K; j += 256) out_idx[(long)img * K + j] = (j < k) ? (int)(sel.keys[j] & 0xffffffffull) : -1;
 }
 
 // Commonsense filter of eval_cs / train_cs (reference evaluator.py:189-194,261-266): a candidate whose
 // (subject class, predicate, object class) triplet is in the "violated" set or is not in the "aligned" set gets
-// confidence -inf.  The Python-set membership tests become two bit lookups in C*R*C-bit device bitmaps.
+// confidence -inf.  The Python-set membership tests become two bit lookups in C*R*C-bit device bitmaps (triplet_bit, csrc/eval_geom.h).
 __global__ void commonsense_filter_kernel(const long* __restrict__ scat, const long* __restrict__ pred, const long* __restrict__ ocat,
                                           float* __restrict__ conf, int n, const unsigned* __restrict__ aligned,
                                           const unsigned* __restrict__ violated, int C, int R) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const long s = scat[i], r = pred[i], o = ocat[i];
-    bool keep = false;
-    if (s >= 0 && s < C && o >= 0 && o < C && r >= 0 && r < R) {
-        const long bit = (s * R + r) * C + o;
-        const bool in_yes = (aligned[bit >> 5] >> (bit & 31)) & 1u;
-        const bool in_no = (violated[bit >> 5] >> (bit & 31)) & 1u;
-        keep = in_yes && !in_no;
-    }
-    if (!keep) conf[i] = -INFINITY;
+    if (triplet_bits(aligned, violated, scat[i], pred[i], ocat[i], C, R) != 1u) conf[i] = -INFINITY;      // keep = aligned and not violated
 }
 
 // train_cs (reference train_utils.py:36-50): per candidate (pair, super-category) flags "triplet not in the aligned set"
@@ -136,14 +53,9 @@ __global__ void commonsense_flags_kernel(const long* __restrict__ scat, const lo
     if (i >= n_pairs * n_cand) return;
     const int pr = i / n_cand;
     const long s = scat[pr], o = ocat[pr], r = cand_pred[i];
-    bool in_yes = false, in_no = false;
-    if (s >= 0 && s < C && o >= 0 && o < C && r >= 0 && r < R) {
-        const long bit = (s * R + r) * C + o;
-        in_yes = (aligned[bit >> 5] >> (bit & 31)) & 1u;
-        in_no = (violated[bit >> 5] >> (bit & 31)) & 1u;
-    }
-    weak[i] = in_yes ? 0.f : 1.f;
-    strong[i] = in_no ? 1.f : 0.f;
+    const unsigned in = triplet_bits(aligned, violated, s, r, o, C, R);
+    weak[i] = (in & 1u) ? 0.f : 1.f;
+    strong[i] = (in & 2u) ? 1.f : 0.f;
 }
 
 // Recall@K hit test (reference evaluator.py:306-356, Top-3 variant :720-760): for every connected ground-truth triple, the rank
@@ -160,50 +72,27 @@ struct RecallParams {
     int* hit;
 };
 
-__device__ __forceinline__ int slice_clip(float v, int F) {           // int(v) then Python slice clipping on an axis of length F
-    int i = (int)v;
-    return i < 0 ? max(i + F, 0) : min(i, F);
-}
-__device__ __forceinline__ bool grid_iou_ok(const float* a, const float* b, int F, double thr) {
-    const int ax0 = slice_clip(a[0], F), ax1 = slice_clip(a[1], F), ay0 = slice_clip(a[2], F), ay1 = slice_clip(a[3], F);
-    const int bx0 = slice_clip(b[0], F), bx1 = slice_clip(b[1], F), by0 = slice_clip(b[2], F), by1 = slice_clip(b[3], F);
-    const int aa = max(ax1 - ax0, 0) * max(ay1 - ay0, 0), ab = max(bx1 - bx0, 0) * max(by1 - by0, 0);
-    int inter = max(min(ax1, bx1) - max(ax0, bx0), 0) * max(min(ay1, by1) - max(ay0, by0), 0);
-    if (aa <= 0 || ab <= 0) inter = 0;
-    const int uni = aa + ab - inter;
-    const double iou = uni > 0 ? (double)inter / (double)uni : 0.0;
-    return iou >= thr;
-}
-
+// The box tables come from the caller with no alignment promise, so their rows are read with the four-load load_box.
 __global__ __launch_bounds__(256) void recall_hits_kernel(const RecallParams p) {
-    const int lane = threadIdx.x & 63;
     const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (t >= p.n_t) return;
     const int row = p.t_row[t], cnt = p.keep_cnt[row];
     const long rel = p.t_rel[t], sc = p.t_scat[t], oc = p.t_ocat[t];
-    int hit = p.K;
-    for (int j0 = 0; j0 < cnt; j0 += 64) {
-        const int j = j0 + lane;
-        bool ok = false;
-        if (j < cnt) {
-            const long c = p.keep_pos[(long)row * p.K + j];
-            const long cs = p.c_scat[c], co = p.c_ocat[c];
-            bool label = (cs == sc) && (co == oc);
-            if (p.equiv && !label) {
-                const bool in = sc >= 0 && sc < p.n_equiv && oc >= 0 && oc < p.n_equiv && cs >= 0 && cs < p.n_equiv && co >= 0 && co < p.n_equiv;
-                label = in && p.equiv[sc * p.n_equiv + cs] && p.equiv[oc * p.n_equiv + co];
-            }
-            if (label) {
-                bool pred = false;
-                for (int k = 0; k < p.n_pred; ++k) pred |= p.c_pred[c * p.n_pred + k] == rel;
-                ok = pred && grid_iou_ok(p.t_sbox + 4L * t, p.c_sbox + 4 * c, p.F, p.iou_thresh) &&
-                     grid_iou_ok(p.t_obox + 4L * t, p.c_obox + 4 * c, p.F, p.iou_thresh);
-            }
+    const int hit = first_match_rank(cnt, p.K, [&](int j) {
+        const long c = p.keep_pos[(long)row * p.K + j];
+        const long cs = p.c_scat[c], co = p.c_ocat[c];
+        bool label = (cs == sc) && (co == oc);
+        if (p.equiv && !label) {
+            const bool in = sc >= 0 && sc < p.n_equiv && oc >= 0 && oc < p.n_equiv && cs >= 0 && cs < p.n_equiv && co >= 0 && co < p.n_equiv;
+            label = in && p.equiv[sc * p.n_equiv + cs] && p.equiv[oc * p.n_equiv + co];
         }
-        const unsigned long long m = __ballot(ok);
-        if (m) { hit = j0 + __ffsll((long long)m) - 1; break; }
-    }
-    if (lane == 0) p.hit[t] = hit;
+        if (!label) return false;
+        bool pred = false;
+        for (int k = 0; k < p.n_pred; ++k) pred |= p.c_pred[c * p.n_pred + k] == rel;
+        return pred && box_iou_ok(load_box(p.t_sbox + 4L * t, p.F), load_box(p.c_sbox + 4 * c, p.F), p.iou_thresh) &&
+               box_iou_ok(load_box(p.t_obox + 4L * t, p.F), load_box(p.c_obox + 4 * c, p.F), p.iou_thresh);
+    });
+    if ((threadIdx.x & 63) == 0) p.hit[t] = hit;
 }
 
 extern "C" {

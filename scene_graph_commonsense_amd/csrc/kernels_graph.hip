@@ -3,6 +3,8 @@
 // :465-503 the ranked edge list).  The evaluator route to the same lists appends int64 copies of every candidate to the
 // Evaluator's state, permutes them into append order, filters them and then groups and ranks them (csrc/kernels_eval.hip).
 #include "common.h"
+#include "eval_geom.h"
+#include "rank_select.h"
 
 struct GraphParams {
     const float* cand_conf; const int* cand_pred; int rep;            // [P][rep] per-pair candidates of the head (rep = 1 or 3)
@@ -12,21 +14,17 @@ struct GraphParams {
     const unsigned char* included;                                    // [P] 0 = the pair is no candidate at all, or NULL
     const int* ptr; const int* list;                                  // [B+1], [ptr[B]] pair rows of every image, ascending; list NULL = identity
     const int* sub_idx; const int* obj_idx; const long* cats;         // [P], [P], [n_obj]; NULL -> subject / object come back -1
-    const unsigned* aligned; const unsigned* violated; int C, R;      // commonsense bitmaps (sgc_commonsense_filter's layout) or NULL
+    const unsigned* aligned; const unsigned* violated; int C, R;      // commonsense bitmaps (triplet_bits' layout) or NULL
     int slot_major, K;
     int* out_pair; int* out_slot; int* out_pred; int* out_sub; int* out_obj; float* out_score;      // [B][K]
     int* out_count; int* out_finite;                                  // [B]
 };
 
-enum { GRAPH_THREADS = 1024, GRAPH_WAVES = GRAPH_THREADS / 64, GRAPH_CACHE = 12288 };     // 48 KiB of cached keys: 64 objects x rep 3
+enum { GRAPH_THREADS = 1024, GRAPH_CACHE = 12288 };     // 48 KiB of cached keys: 64 objects x rep 3
 
 // ascending uint order == ascending float order; every NaN ranks first (as torch.sort puts it); 0 is below -inf and marks a
 // slot that is no candidate
-__device__ __forceinline__ unsigned graph_key(float f) {
-    if (f != f) return 0xffffffffu;
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
+__device__ __forceinline__ unsigned graph_key(float f) { return f != f ? 0xffffffffu : order_key(f); }
 
 // local slot j of an image with m listed pairs -> (position in its list, super-category slot).  The tie order IS the order of j.
 __device__ __forceinline__ void graph_decode(const GraphParams& g, int j, int m, int& i, int& s) {
@@ -43,13 +41,7 @@ __device__ __forceinline__ float graph_score(const GraphParams& g, int p, int s,
     bool keep = !(g.mask && g.mask[p] == 0);
     if (keep && g.aligned) {
         const long sc = g.cats[g.sub_idx[p]], oc = g.cats[g.obj_idx[p]], r = g.cand_pred[(long)p * g.rep + s];
-        keep = false;
-        if (sc >= 0 && sc < g.C && oc >= 0 && oc < g.C && r >= 0 && r < g.R) {
-            const long bit = (sc * g.R + r) * g.C + oc;
-            const bool in_yes = (g.aligned[bit >> 5] >> (bit & 31)) & 1u;
-            const bool in_no = (g.violated[bit >> 5] >> (bit & 31)) & 1u;
-            keep = in_yes && !in_no;
-        }
+        keep = triplet_bits(g.aligned, g.violated, sc, r, oc, g.C, g.R) == 1u;      // aligned and not violated
     }
     if (!keep) c = -INFINITY;
     return c + g.conn[p];
@@ -64,23 +56,19 @@ __device__ __forceinline__ unsigned graph_slot_key(const GraphParams& g, int b0,
     return valid ? graph_key(c) : 0u;
 }
 
-// One workgroup per image, the selection scheme of topk_kernel (csrc/kernels_eval.hip): the keys of the image's slots are formed
-// once and kept in LDS (slots past GRAPH_CACHE are formed again in every pass), radix-select of the K-th largest, everything above
-// it plus the earliest ties by ordered compaction, bitonic sort of the <= 128 survivors by (confidence desc, slot asc).
+// One workgroup per image: the keys of the image's slots are formed once and kept in LDS (slots past GRAPH_CACHE are formed again
+// every time the selection asks for them), then block_topk (csrc/rank_select.h) ranks them by (confidence desc, slot asc).
 // Tie order = the reference's append order.  Pair-major (pair, slot) is right for fused scenes: a direction-step holds at most
 // one pair of an image, so the step's blocked [geo | poss | sem] append order and the pair-major order coincide PER IMAGE.
 // Slot-major (slot, pair) is right for one head.candidates call appended with call_sizes = [M].
 __global__ __launch_bounds__(GRAPH_THREADS) void scene_graph_topk_kernel(const GraphParams g) {
     __shared__ unsigned cache[GRAPH_CACHE];
-    __shared__ unsigned hist[256];
-    __shared__ unsigned s_prefix, s_mask;
-    __shared__ int s_remaining, s_cnt, s_base, s_valid, s_finite, wave_cnt[GRAPH_WAVES];
-    __shared__ unsigned long long keys[128];
-    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, K = g.K;
+    __shared__ TopkScratch<GRAPH_THREADS> sel;
+    __shared__ int s_valid, s_finite;
+    const int img = blockIdx.x, tid = threadIdx.x, lane = tid & 63, K = g.K;
     const int b0 = g.ptr[img], m = g.ptr[img + 1] - b0;
     const int n = m * g.rep;
-    if (tid < 128) keys[tid] = ~0ull;
-    if (tid == 0) { s_prefix = 0; s_mask = 0; s_cnt = 0; s_valid = 0; s_finite = 0; }
+    if (tid == 0) { s_valid = 0; s_finite = 0; }
     __syncthreads();
     for (int j0 = 0; j0 < n; j0 += GRAPH_THREADS) {
         const int j = j0 + tid;
@@ -93,82 +81,9 @@ __global__ __launch_bounds__(GRAPH_THREADS) void scene_graph_topk_kernel(const G
         if (lane == 0 && bal) atomicAdd(&s_valid, __popcll(bal));
     }
     __syncthreads();
+    // k <= candidates, so the K-th largest key belongs to a candidate: it is > 0 and a non-candidate slot is never taken
     const int k = min(K, s_valid);
-    if (tid == 0) s_remaining = k;
-    __syncthreads();
-#define GRAPH_KEY(j) ((j) < GRAPH_CACHE ? cache[j] : graph_slot_key(g, b0, m, (j)))
-    if (k > 0) {
-        for (int pass = 3; pass >= 0; --pass) {
-            if (tid < 256) hist[tid] = 0;
-            __syncthreads();
-            const unsigned prefix = s_prefix, mask = s_mask;
-            for (int j = tid; j < n; j += GRAPH_THREADS) {
-                const unsigned key = GRAPH_KEY(j);
-                if ((key & mask) == prefix) atomicAdd(&hist[(key >> (8 * pass)) & 255u], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int cum = 0, rem = s_remaining;
-                for (int bk = 255; bk >= 0; --bk) {
-                    const int hv = (int)hist[bk];
-                    if (cum + hv >= rem) {
-                        s_prefix = prefix | ((unsigned)bk << (8 * pass));
-                        s_mask = mask | (0xffu << (8 * pass));
-                        s_remaining = rem - cum;
-                        break;
-                    }
-                    cum += hv;
-                }
-            }
-            __syncthreads();
-        }
-        // the K-th largest key belongs to a candidate (k <= candidates), so thr > 0 and a non-candidate slot is never taken;
-        // fewer than k keys lie above thr, so the unordered positions stay inside keys[]
-        const unsigned thr = s_prefix;
-        for (int j = tid; j < n; j += GRAPH_THREADS) {
-            const unsigned key = GRAPH_KEY(j);
-            if (key > thr) {
-                const int pos = atomicAdd(&s_cnt, 1);
-                if (pos < 128) keys[pos] = ((unsigned long long)(~key) << 32) | (unsigned)j;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) s_base = s_cnt;
-        __syncthreads();
-        for (int c0 = 0; c0 < n; c0 += GRAPH_THREADS) {
-            if (s_base >= k) break;
-            const int j = c0 + tid;
-            const bool flag = j < n && GRAPH_KEY(j) == thr;
-            const unsigned long long bal = __ballot(flag);
-            const int within = __popcll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_cnt[wv] = __popcll(bal);
-            __syncthreads();
-            int off = s_base + within, total = 0;
-            for (int w2 = 0; w2 < GRAPH_WAVES; ++w2) {
-                if (w2 < wv) off += wave_cnt[w2];
-                total += wave_cnt[w2];
-            }
-            if (flag && off < k) keys[off] = ((unsigned long long)(~thr) << 32) | (unsigned)j;
-            __syncthreads();
-            if (tid == 0) s_base += total;
-            __syncthreads();
-        }
-        // bitonic sort of 128 keys, ascending ( = confidence descending, slot ascending)
-        for (int size = 2; size <= 128; size <<= 1) {
-            for (int stride = size >> 1; stride > 0; stride >>= 1) {
-                __syncthreads();
-                if (tid < 64) {
-                    const int lo = 2 * tid - (tid & (stride - 1));
-                    const int hi = lo + stride;
-                    const bool up = ((lo & size) == 0);
-                    const unsigned long long a = keys[lo], bb = keys[hi];
-                    if ((a > bb) == up) { keys[lo] = bb; keys[hi] = a; }
-                }
-            }
-        }
-        __syncthreads();
-    }
-#undef GRAPH_KEY
+    block_topk<GRAPH_THREADS>(sel, n, k, [&](int j) { return j < GRAPH_CACHE ? cache[j] : graph_slot_key(g, b0, m, j); });
     // epilogue: the ranked edges (evaluator.py:482-503 reads the same fields of the ranked candidates); K <= 128 < GRAPH_THREADS
     bool finite = false;
     if (tid < K) {
@@ -176,7 +91,7 @@ __global__ __launch_bounds__(GRAPH_THREADS) void scene_graph_topk_kernel(const G
         int pair = -1, slot = -1, pred = -1, sub = -1, obj = -1;
         float score = -INFINITY;
         if (tid < k) {
-            const int j = (int)(keys[tid] & 0xffffffffull);
+            const int j = (int)(sel.keys[tid] & 0xffffffffull);
             int i;
             graph_decode(g, j, m, i, slot);
             pair = g.list ? g.list[b0 + i] : b0 + i;

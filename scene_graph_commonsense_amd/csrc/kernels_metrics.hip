@@ -5,48 +5,9 @@
 // ranked subject and object.  The counters are 64-bit integers updated with atomicAdd, so their sums do not depend on the order
 // in which the wavefronts arrive.
 #include "common.h"
+#include "eval_geom.h"
 
 enum { METRIC_MAX_KS = 8 };
-
-struct GridBox { int x0, x1, y0, y1; };                                // half-open, after int() truncation and slice clipping
-
-__device__ __forceinline__ int metric_clip(float v, int F) {           // mask[int(a):int(b)] on an axis of length F (slice_clip of kernels_eval.hip)
-    const int i = (int)v;
-    return i < 0 ? max(i + F, 0) : min(i, F);
-}
-__device__ __forceinline__ GridBox load_box(const float* __restrict__ boxes, int o, int F) {      // rows of 4 f32: one 16-byte load
-    const f32x4 b = *reinterpret_cast<const f32x4*>(boxes + 4L * o);
-    return GridBox{metric_clip(b[0], F), metric_clip(b[1], F), metric_clip(b[2], F), metric_clip(b[3], F)};
-}
-// An empty box (x1 <= x0 or y1 <= y0) stays empty under box_and, so its area is 0 without a special case.
-__device__ __forceinline__ GridBox box_and(const GridBox a, const GridBox b) {
-    return GridBox{max(a.x0, b.x0), min(a.x1, b.x1), max(a.y0, b.y0), min(a.y1, b.y1)};
-}
-__device__ __forceinline__ int box_area(const GridBox a) { return max(a.x1 - a.x0, 0) * max(a.y1 - a.y0, 0); }
-
-// IoU of two rasterised rectangles >= thr; union == 0 -> IoU 0 (evaluator.py:84-94; grid_iou_ok of kernels_eval.hip)
-__device__ __forceinline__ bool box_iou_ok(const GridBox a, const GridBox b, double thr) {
-    const int aa = box_area(a), ab = box_area(b), inter = box_area(box_and(a, b));
-    const int uni = aa + ab - inter;
-    const double iou = uni > 0 ? (double)inter / (double)uni : 0.0;
-    return iou >= thr;
-}
-// |X & (ts | to)| for a rectangle X: inclusion-exclusion over rectangles, whose intersections are rectangles again
-__device__ __forceinline__ int area_in_pair(const GridBox x, const GridBox ts, const GridBox to) {
-    const GridBox xs = box_and(x, ts);
-    return box_area(xs) + box_area(box_and(x, to)) - box_area(box_and(xs, to));
-}
-// IoU of the masks (subject | object) of a prediction and of a target >= thr (evaluator.py:97-115), in exact cell counts on a grid
-// of any size: |P & T| = |S & T| + |O & T| - |S & O & T| with every term a sum of rectangle areas.  union == 0 -> IoU 0.
-__device__ __forceinline__ bool union_iou_ok(const GridBox s, const GridBox o, const GridBox ts, const GridBox to, double thr) {
-    const GridBox so = box_and(s, o);
-    const int inter = area_in_pair(s, ts, to) + area_in_pair(o, ts, to) - area_in_pair(so, ts, to);
-    const int ap = box_area(s) + box_area(o) - box_area(so);
-    const int at = box_area(ts) + box_area(to) - box_area(box_and(ts, to));
-    const int uni = ap + at - inter;
-    const double iou = uni > 0 ? (double)inter / (double)uni : 0.0;
-    return iou >= thr;
-}
 
 struct RecallAccParams {
     const int* out_pair; const int* out_pred; const int* out_sub; const int* out_obj;      // [n_img][K] ranked lists
@@ -57,15 +18,15 @@ struct RecallAccParams {
     const unsigned char* included; int P;                   // [P] kept steps or NULL
     const int* img_targets;                                 // [n_img] connected targets of the kept steps per image (Top-3)
     int ks[METRIC_MAX_KS]; int n_k;
-    const unsigned* zs; int C, R;                           // zero-shot bitmap (bit (s*R + r)*C + o) or NULL
+    const unsigned* zs; int C, R;                           // zero-shot bitmap (triplet_bit's layout) or NULL
     int F; double iou_thresh;
     unsigned long long* hits; unsigned long long* hits_pc; unsigned long long* tgt; unsigned long long* tgt_pc;              // [n_k], [n_k][R], [1], [R]
     unsigned long long* zs_hits; unsigned long long* zs_hits_pc; unsigned long long* zs_tgt; unsigned long long* zs_tgt_pc;  // the zero-shot twins
 };
 
-// One wavefront per pair row; rows that are no connected target of a kept step leave at once.  The scan is recall_hits_kernel's:
-// lanes take ranks l, l + 64; labels, both grid IoUs and the predicate must match; a candidate whose labels and boxes match but
-// whose predicate differs does not end the scan; the first matching rank comes from a ballot; -inf candidates take part.
+// One wavefront per pair row; rows that are no connected target of a kept step leave at once.  The scan is first_match_rank
+// (csrc/eval_geom.h) with recall_hits_kernel's test: labels, both grid IoUs and the predicate must match; a candidate whose labels
+// and boxes match but whose predicate differs does not end the scan; -inf candidates take part.
 __global__ __launch_bounds__(256) void recall_accumulate_kernel(const RecallAccParams p) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -77,36 +38,24 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const RecallAccP
     const long sc = p.cats[ts], oc = p.cats[to];
     const GridBox tsb = load_box(p.boxes, ts, p.F), tob = load_box(p.boxes, to, p.F);
     const int cnt = min(p.out_count[img], p.K);
-    int hit = p.K;
-    for (int j0 = 0; j0 < cnt; j0 += 64) {
-        const int j = j0 + lane;
-        bool ok = false;
-        if (j < cnt) {
-            const long o = (long)img * p.K + j;
-            const int cs = p.out_sub[o], co = p.out_obj[o];
-            if (cs >= 0 && cs < p.n_obj && co >= 0 && co < p.n_obj && p.cats[cs] == sc && p.cats[co] == oc) {
-                bool pred = false;
-                if (p.n_pred == 1) {
-                    pred = p.out_pred[o] == rel;
-                } else {
-                    const int pr = p.out_pair[o];
-                    if (pr >= 0 && pr < p.P)
-                        for (int k = 0; k < 3; ++k) pred |= p.cand_pred[3L * pr + k] == rel;
-                }
-                ok = pred && box_iou_ok(tsb, load_box(p.boxes, cs, p.F), p.iou_thresh) &&
-                     box_iou_ok(tob, load_box(p.boxes, co, p.F), p.iou_thresh);
-            }
+    const int hit = first_match_rank(cnt, p.K, [&](int j) {
+        const long o = (long)img * p.K + j;
+        const int cs = p.out_sub[o], co = p.out_obj[o];
+        if (!(cs >= 0 && cs < p.n_obj && co >= 0 && co < p.n_obj && p.cats[cs] == sc && p.cats[co] == oc)) return false;
+        bool pred = false;
+        if (p.n_pred == 1) {
+            pred = p.out_pred[o] == rel;
+        } else {
+            const int pr = p.out_pair[o];
+            if (pr >= 0 && pr < p.P)
+                for (int k = 0; k < 3; ++k) pred |= p.cand_pred[3L * pr + k] == rel;
         }
-        const unsigned long long m = __ballot(ok);
-        if (m) { hit = j0 + __ffsll((long long)m) - 1; break; }
-    }
+        return pred && box_iou_ok(tsb, load_box(p.boxes, cs, p.F), p.iou_thresh) &&
+               box_iou_ok(tob, load_box(p.boxes, co, p.F), p.iou_thresh);
+    });
     if (lane != 0) return;
     const bool cls = rel >= 0 && rel < p.R;
-    bool zs = false;
-    if (p.zs && cls && sc >= 0 && sc < p.C && oc >= 0 && oc < p.C) {
-        const long bit = (sc * p.R + rel) * p.C + oc;
-        zs = (p.zs[bit >> 5] >> (bit & 31)) & 1u;
-    }
+    const bool zs = p.zs && triplet_bit(p.zs, sc, rel, oc, p.C, p.R);
     const int n_t = p.n_pred == 3 ? p.img_targets[img] : 0;
     for (int i = 0; i < p.n_k; ++i) {
         // evaluator.py:435 `hit < k and hit < count`; Top-3 :668 `hit < count and hit < max(k, targets of the image)`

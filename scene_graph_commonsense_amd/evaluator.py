@@ -80,19 +80,8 @@ def grid_iou_matrix(bt: np.ndarray, bp: np.ndarray, F: int) -> np.ndarray:
 def rank_topk(conf: torch.Tensor, which: torch.Tensor, K: int):
     """Group candidates per image and rank each group with the HIP top-K kernel.
     Returns (images [n_img], per-image candidate positions (indices into the flat arrays) list, top [n_img,K] local idx)."""
-    if not conf.is_cuda:
-        raise RuntimeError("Evaluator ranking runs on the GPU (sgc_topk_per_image); move the evaluator inputs to cuda")
-    lib = _lib.load()
-    images, counts = torch.unique(which, return_counts=True)
-    order = torch.sort(which, stable=True)[1]                       # grouped by image, append order kept
-    conf_g = conf[order].contiguous().float()
-    seg = torch.zeros(len(images) + 1, dtype=torch.int32, device=conf.device)
-    seg[1:] = torch.cumsum(counts, 0).int()
-    out_idx = torch.empty(len(images), K, dtype=torch.int32, device=conf.device)
-    out_cnt = torch.empty(len(images), dtype=torch.int32, device=conf.device)
-    _lib.check(lib.sgc_topk_per_image(_lib.ptr(conf_g), _lib.ptr(seg), len(images), K, _lib.ptr(out_idx), _lib.ptr(out_cnt),
-                                      _lib.stream_ptr()), "sgc_topk_per_image")
-    return images.cpu().numpy(), order.cpu().numpy(), seg.cpu().numpy(), out_idx.cpu().numpy(), out_cnt.cpu().numpy()
+    images, _, cnt, top, seg, order = rank_topk_device(conf, which, K)
+    return images.cpu().numpy(), order.cpu().numpy(), seg.cpu().numpy(), top.cpu().numpy(), cnt.cpu().numpy()
 
 
 def first_hit(label_ok: np.ndarray, iou_ok: np.ndarray, pred_ok: np.ndarray) -> np.ndarray:

@@ -301,3 +301,175 @@ def test_skipping_filtered_pairs_keeps_recall():
         np.testing.assert_array_equal(a[3][k], b[3][k])
     # the skip really skipped something
     assert float((b[6].relation.abs().sum(1) == 0).float().mean()) > 0.2
+
+
+@pytest.mark.parametrize("K", [1, 20, 128])
+def test_both_rankers_agree_on_one_confidence_vector(K):
+    """sgc_topk_per_image (256 threads, keys from memory) and sgc_scene_graph_topk (1024 threads, keys cached in LDS up to 12288)
+    run the one block-wide selection of csrc/rank_select.h: on the same flat confidences they return the same image-local indices
+    and counts, and both equal the stable descending sort.  The sizes straddle every loop bound of the two instantiations.
+    conn is -0.0, the additive identity of IEEE floats (x + -0.0 == x bit for bit; +0.0 would turn a -0.0 confidence into +0.0).
+    The kernels order by bit pattern, so +0.0 ranks ahead of -0.0 (tests/mining_cases.py): the host reference is built that way."""
+    from scene_graph_commonsense_amd import _lib
+    from scene_graph_commonsense_amd.evaluator import rank_topk_device
+    from scene_graph_commonsense_amd.scene_graph import rank_scene_graphs
+    sizes = [0, 1, K - 1, K, K + 1, 255, 256, 257, 1023, 1025, 12289]
+    g = torch.Generator().manual_seed(K)
+    n = sum(sizes)
+    conf = torch.randn(n, generator=g)
+    u = torch.rand(n, generator=g)
+    conf[u < 0.3] = -float("inf")                        # many ties at -inf
+    conf[(u >= 0.3) & (u < 0.5)] = 0.25                  # ties at a finite value
+    conf[(u >= 0.5) & (u < 0.6)] = 0.0                   # +0.0 next to -0.0
+    conf[(u >= 0.6) & (u < 0.7)] = -0.0
+    assert not torch.isnan(conf).any()
+    ptr = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32)
+    which = torch.repeat_interleave(torch.arange(len(sizes)), torch.tensor(sizes))          # grouped already: order = identity
+    dev = "cuda:0"
+    conf_d, ptr_d = conf.to(dev), ptr.to(dev)
+    images, _, cnt, top, seg, order = rank_topk_device(conf_d, which.to(dev), K)
+    graphs = rank_scene_graphs(conf_d, torch.zeros(n, dtype=torch.int32, device=dev), torch.full((n,), -0.0, device=dev), ptr_d,
+                               top_k=K, slot_major=False)
+    # the top-K kernel once more on the graph kernel's own segments, which include the empty images
+    top_all = torch.empty(len(sizes), K, dtype=torch.int32, device=dev)
+    cnt_all = torch.empty(len(sizes), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().sgc_topk_per_image(_lib.ptr(conf_d), _lib.ptr(ptr_d), len(sizes), K, _lib.ptr(top_all), _lib.ptr(cnt_all),
+                                              _lib.stream_ptr()), "sgc_topk_per_image")
+    images, cnt, top, top_all, cnt_all = (t.cpu().numpy() for t in (images, cnt, top, top_all, cnt_all))
+    np.testing.assert_array_equal(order.cpu().numpy(), np.arange(n))
+    g_cnt, g_pair, g_slot = graphs.count.cpu().numpy(), graphs.pair.cpu().numpy(), graphs.slot.cpu().numpy()
+    g_local = np.where(g_pair >= 0, g_pair - ptr.numpy()[:-1, None], -1)
+    np.testing.assert_array_equal(images, [i for i, s in enumerate(sizes) if s > 0])          # images without a candidate have no row
+    np.testing.assert_array_equal(top, top_all[images])
+    np.testing.assert_array_equal(cnt, cnt_all[images])
+    np.testing.assert_array_equal(g_cnt, cnt_all)
+    np.testing.assert_array_equal(g_local, top_all)
+    assert (g_slot[g_pair >= 0] == 0).all()
+    c64 = conf.numpy().astype(np.float64)
+    for b, size in enumerate(sizes):
+        c = c64[ptr[b]:ptr[b + 1]]
+        ref = np.lexsort((np.arange(size), np.signbit(c) & (c == 0), -c))[:K]
+        assert cnt_all[b] == min(K, size)
+        np.testing.assert_array_equal(top_all[b, :cnt_all[b]], ref)
+        assert (top_all[b, cnt_all[b]:] == -1).all()
+
+
+# C = 5 classes, R = 3 predicates: 75 bits.  aligned = {bit 0, bit 74 (the last valid one)}, violated = {bit 74}.
+# (subject, predicate, object) -> (in aligned, in violated); a label out of range is in neither set, also where the linear index
+# (s*R + r)*C + o of the out-of-range triplet lands on a set bit.
+_TRIPLET_TABLE = [
+    ((0, 0, 0), (True, False)),          # bit 0
+    ((4, 2, 4), (True, True)),           # bit 74
+    ((3, 0, 0), (False, False)),         # in range (R is a valid class), bit clear
+    ((-1, 0, 0), (False, False)),
+    ((0, -1, 0), (False, False)),
+    ((0, 0, -1), (False, False)),
+    ((5, 0, 0), (False, False)),         # subject = C
+    ((0, 0, 5), (False, False)),         # object = C
+    ((0, 3, 0), (False, False)),         # predicate = R
+    ((0, 5, 0), (False, False)),         # predicate = C
+    ((-1, 3, 0), (False, False)),        # (-3 + 3)*5 + 0 = 0: lands on bit 0
+    ((0, -1, 5), (False, False)),        # (0 - 1)*5 + 5 = 0: lands on bit 0
+    ((5, -1, 4), (False, False)),        # (15 - 1)*5 + 4 = 74: lands on bit 74
+    ((4, 3, -1), (False, False)),        # (12 + 3)*5 - 1 = 74: lands on bit 74
+]
+
+
+@pytest.mark.parametrize("entry", ["sgc_commonsense_filter", "sgc_commonsense_flags", "rank_scene_graphs"])
+def test_out_of_range_labels_are_in_no_triplet_set(entry):
+    from scene_graph_commonsense_amd import _lib
+    from scene_graph_commonsense_amd.commonsense import TripletBitmaps
+    from scene_graph_commonsense_amd.scene_graph import rank_scene_graphs
+    dev = "cuda:0"
+    bm = TripletBitmaps([(0, 0, 0), (4, 2, 4)], [(4, 2, 4)], 5, 3, dev)
+    words = lambda t: t.cpu().numpy().view(np.uint32).tolist()
+    assert words(bm.aligned) == [1, 0, 1 << 10] and words(bm.violated) == [0, 0, 1 << 10]          # bit 74 = bit 10 of word 2
+    s, r, o = (torch.tensor([t[0][i] for t in _TRIPLET_TABLE], dtype=torch.int64, device=dev) for i in range(3))
+    in_yes = np.array([t[1][0] for t in _TRIPLET_TABLE])
+    in_no = np.array([t[1][1] for t in _TRIPLET_TABLE])
+    keep = in_yes & ~in_no
+    n = len(_TRIPLET_TABLE)
+    if entry == "sgc_commonsense_filter":
+        conf = torch.arange(1, n + 1, dtype=torch.float32, device=dev)
+        got = bm.filter_(s, r, o, conf.clone()).cpu().numpy()
+        np.testing.assert_array_equal(got, np.where(keep, conf.cpu().numpy(), -np.inf))
+    elif entry == "sgc_commonsense_flags":
+        weak, strong = torch.full((n, 1), -1.0, device=dev), torch.full((n, 1), -1.0, device=dev)
+        pred = r.int().view(n, 1).contiguous()
+        _lib.check(_lib.load().sgc_commonsense_flags(_lib.ptr(s), _lib.ptr(o), _lib.ptr(pred), n, 1, _lib.ptr(bm.aligned), _lib.ptr(bm.violated),
+                                                     bm.C, bm.R, _lib.ptr(weak), _lib.ptr(strong), _lib.stream_ptr()), "sgc_commonsense_flags")
+        np.testing.assert_array_equal(weak.cpu().numpy()[:, 0], np.where(in_yes, 0.0, 1.0))
+        np.testing.assert_array_equal(strong.cpu().numpy()[:, 0], np.where(in_no, 1.0, 0.0))
+    else:
+        cats = torch.tensor([0, 1, 2, 3, 4, 5, -1], dtype=torch.int64, device=dev)          # object i has class i; 5 -> C, 6 -> -1
+        obj_of = lambda lab: torch.where(lab < 0, torch.full_like(lab, 6), lab).int()
+        conf = torch.arange(1, n + 1, dtype=torch.float32, device=dev)
+        graphs = rank_scene_graphs(conf, r.int(), torch.zeros(n, device=dev), torch.tensor([0, n], dtype=torch.int32, device=dev), top_k=n,
+                                   sub_idx=obj_of(s), obj_idx=obj_of(o), cats=cats, bitmaps=bm)
+        assert int(graphs.count[0]) == n and int(graphs.n_finite[0]) == int(keep.sum())
+        score = np.empty(n, dtype=np.float32)
+        score[graphs.pair[0].cpu().numpy()] = graphs.score[0].cpu().numpy()
+        np.testing.assert_array_equal(score, np.where(keep, conf.cpu().numpy(), -np.inf))
+
+
+def test_recall_hits_matches_the_host_grid_iou():
+    """sgc_recall_hits on the shared grid geometry (csrc/eval_geom.h) against grid_iou_matrix / first_hit of evaluator.py, F = 32:
+    an empty box, negative coordinates (Python slice clipping), a coordinate above F, an IoU equal to the threshold, a first hit at
+    rank 64 and at rank 70 (second trip of the scan) behind a label-and-box match whose predicate differs, a match past the count."""
+    from scene_graph_commonsense_amd.evaluator import first_hit, grid_iou_matrix, recall_hits
+    F, K, thr, n, cnt = 32, 128, 0.5, 110, 100
+    B = (5.9, 20.2, 1.5, 7.5)
+    c_lab = np.full((n, 2), 9, dtype=np.int64)
+    c_pred = np.zeros(n, dtype=np.int64)
+    c_sbox = np.tile(np.float32([1, 2, 1, 2]), (n, 1))
+    c_obox = np.tile(np.float32(B), (n, 1))
+    rank_to_cand = np.arange(n)[::-1].copy()                                     # rank j is candidate n-1-j
+
+    def plant(rank, lab, pred, sbox):
+        c = rank_to_cand[rank]
+        c_lab[c], c_pred[c], c_sbox[c] = lab, pred, sbox
+    targets = []                                                                 # (row, rel, labels, sbox, expected rank)
+    A = (2, 10, 3, 9)
+    plant(3, (1, 2), 2, A); plant(70, (1, 2), 1, A); plant(90, (1, 2), 1, A)
+    targets.append((0, 1, (1, 2), A, 70))                                        # rank 3 matches but for the predicate
+    plant(5, (3, 3), 0, (10, 10, 4, 8))
+    targets.append((0, 0, (3, 3), (10, 10, 4, 8), K))                            # empty on both sides: union 0 -> IoU 0
+    plant(6, (3, 4), 0, (28, 32, 0, 5))
+    targets.append((0, 0, (3, 4), (-4, 10, 0, 5), K))                            # int(-4) -> 28 > 10: empty, not [28, 32)
+    plant(7, (4, 4), 2, (22, 30, 0, 5))
+    targets.append((0, 2, (4, 4), (-10, -2, -40, 5.5), 7))                       # [-10:-2] = [22, 30), [-40:5] = [0, 5)
+    plant(64, (5, 5), 0, (20, 32, 30, 32))
+    targets.append((0, 0, (5, 5), (20.7, 40, 30, 33), 64))                       # clipped to F
+    plant(8, (6, 6), 1, (0, 4, 0, 1.99)); plant(9, (6, 6), 1, (0, 4, 0, 2))
+    targets.append((0, 1, (6, 6), (0, 4, 0, 4), 9))                              # 4/16 < thr at rank 8, 8/16 == thr at rank 9
+    targets.append((0, 0, (7, 7), A, K))                                         # no candidate has the labels
+    plant(105, (8, 8), 0, A)
+    targets.append((0, 0, (8, 8), A, K))                                         # the match lies past keep_cnt
+    targets.append((1, 0, (9, 9), (1, 2, 1, 2), K))                              # an image without ranked candidates
+    keep_pos = np.full((2, K), -1, dtype=np.int32)
+    keep_pos[0, :n] = rank_to_cand
+    keep_cnt = np.array([cnt, 0], dtype=np.int32)
+    t_row = np.array([t[0] for t in targets], dtype=np.int32)
+    t_rel = np.array([t[1] for t in targets], dtype=np.int64)
+    t_lab = np.array([t[2] for t in targets], dtype=np.int64)
+    t_sbox = np.float32([t[3] for t in targets])
+    t_obox = np.tile(np.float32(B), (len(targets), 1))
+    # host reference in ranked order, columns past the image's count switched off
+    ranked = np.where(keep_pos >= 0, keep_pos, 0)[t_row]                         # [T, K]
+    live = np.arange(K)[None, :] < keep_cnt[t_row][:, None]
+    label_ok = (c_lab[ranked, 0] == t_lab[:, None, 0]) & (c_lab[ranked, 1] == t_lab[:, None, 1]) & live
+    pred_ok = c_pred[ranked] == t_rel[:, None]
+    iou_ok = np.zeros_like(live)
+    for t in range(len(targets)):
+        iou_s = grid_iou_matrix(t_sbox[t:t + 1], c_sbox[ranked[t]], F)[0]
+        iou_o = grid_iou_matrix(t_obox[t:t + 1], c_obox[ranked[t]], F)[0]
+        iou_ok[t] = (iou_s >= thr) & (iou_o >= thr)
+    ref = first_hit(label_ok, iou_ok, pred_ok)
+    np.testing.assert_array_equal(ref, [t[4] for t in targets])                 # the cases are what they were built to be
+    dev = "cuda:0"
+    cand = dict(scat=torch.from_numpy(c_lab[:, 0].copy()), ocat=torch.from_numpy(c_lab[:, 1].copy()), pred=torch.from_numpy(c_pred),
+                sbox=torch.from_numpy(c_sbox), obox=torch.from_numpy(c_obox))
+    tg = dict(row=torch.from_numpy(t_row), rel=torch.from_numpy(t_rel), scat=torch.from_numpy(t_lab[:, 0].copy()),
+              ocat=torch.from_numpy(t_lab[:, 1].copy()), sbox=torch.from_numpy(t_sbox), obox=torch.from_numpy(t_obox))
+    got = recall_hits(cand, torch.from_numpy(keep_pos).to(dev), torch.from_numpy(keep_cnt).to(dev), tg, K, F, thr)
+    np.testing.assert_array_equal(got, ref)
