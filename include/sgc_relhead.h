@@ -431,6 +431,25 @@ int sgc_recall_accumulate(const int* out_pair, const int* out_pred, const int* o
                           long* targets, long* targets_pc, long* zs_hits, long* zs_hits_pc, long* zs_targets, long* zs_targets_pc,
                           void* stream);
 
+/* The same counters for SGDET / SGCLS (evaluator.py:272-277, 306-356 with predcls=False; utils.py:355-373): the targets are
+ * ground-truth triples with classes and boxes of their own, one row each of a target table - t_image int32 (row of the ranked
+ * lists), t_rel / t_scat / t_ocat int64, t_sbox / t_obox f32 [n_targets][4] raw (x0,x1,y0,y1), any alignment - and the candidates are
+ * the ranked lists of sgc_scene_graph_topk over the PREDICTED objects (cats, boxes as in sgc_recall_accumulate).  One wavefront per
+ * target.  Skipped and NOT counted as a target: t_rel == -1, t_image outside [0, n_img), out_count[t_image] == 0 (the evaluator
+ * visits the images that own a candidate).  Hit rank = sgc_recall_hits' scan with one predicate per candidate over
+ * min(out_count, K) ranks: labels equal, or with equiv (u8 [n_equiv][n_equiv], NULL = equality only) all four classes in
+ * [0, n_equiv) and equiv[t_scat][candidate's] && equiv[t_ocat][candidate's]; predicate equal; both grid IoUs >= iou_thresh; a
+ * candidate with matching labels and boxes but another predicate does not end the scan; -inf candidates take part.  The hit counts
+ * for k of top_k (HOST array, n_k <= 8) when hit < k and hit < out_count; per-class counters for 0 <= t_rel < R only; the zero-shot
+ * twins by the TARGET's classes. */
+int sgc_recall_accumulate_targets(const int* out_pred, const int* out_sub, const int* out_obj, const int* out_count, int n_img, int K,
+                                  const long* cats, const float* boxes, int n_obj, const int* t_image, const long* t_rel,
+                                  const long* t_scat, const long* t_ocat, const float* t_sbox, const float* t_obox, int n_targets,
+                                  const unsigned char* equiv, int n_equiv, const int* top_k, int n_k, const unsigned* zero_shot, int C,
+                                  int R, int feature_size, double iou_thresh, long* hits, long* hits_pc, long* targets,
+                                  long* targets_pc, long* zs_hits, long* zs_hits_pc, long* zs_targets, long* zs_targets_pc,
+                                  void* stream);
+
 /* OpenImages precision counters on the device (evaluator.py:522-557): one wavefront per (image, rank j < min(n_rank, out_count)) of
  * the same ranked lists; image_ptr [n_img+1] / pair_list: the pair rows of every image (pair_list NULL = the rows image_ptr[b] ..
  * image_ptr[b+1]-1).  Over the image's targets (directed != -1, included != 0) with the candidate's labels and predicate:

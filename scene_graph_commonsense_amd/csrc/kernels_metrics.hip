@@ -9,6 +9,35 @@
 
 enum { METRIC_MAX_KS = 8 };
 
+typedef unsigned long long u64;
+
+// The eight counter arrays of one Recall@K family and what decides their update, shared by the two accumulate kernels.
+struct RecallCounters {
+    int ks[METRIC_MAX_KS]; int n_k;
+    const unsigned* zs; int C, R;                           // zero-shot bitmap (triplet_bit's layout) or NULL
+    u64* hits; u64* hits_pc; u64* tgt; u64* tgt_pc;                  // [n_k], [n_k][R], [1], [R]
+    u64* zs_hits; u64* zs_hits_pc; u64* zs_tgt; u64* zs_tgt_pc;      // the zero-shot twins
+};
+
+// One target with classes (sc, oc), predicate rel and first matching rank `hit` among the cnt ranked candidates of its image
+// (evaluator.py:336-356).  One lane calls this.  top3_targets >= 0: the Top-3 bound max(k, targets of the image); -1: k.
+__device__ __forceinline__ void count_target(const RecallCounters& c, long sc, long rel, long oc, int hit, int cnt, int top3_targets) {
+    const bool cls = rel >= 0 && rel < c.R;
+    const bool zs = c.zs && triplet_bit(c.zs, sc, rel, oc, c.C, c.R);
+    for (int i = 0; i < c.n_k; ++i) {
+        // evaluator.py:435 `hit < k and hit < count`; Top-3 :668 `hit < count and hit < max(k, targets of the image)`
+        const int bound = top3_targets >= 0 ? max(c.ks[i], top3_targets) : c.ks[i];
+        if (hit < cnt && hit < bound) {
+            atomicAdd(c.hits + i, 1ull);
+            if (cls) atomicAdd(c.hits_pc + (long)i * c.R + rel, 1ull);
+            if (zs) { atomicAdd(c.zs_hits + i, 1ull); atomicAdd(c.zs_hits_pc + (long)i * c.R + rel, 1ull); }
+        }
+    }
+    atomicAdd(c.tgt, 1ull);
+    if (cls) atomicAdd(c.tgt_pc + rel, 1ull);
+    if (zs) { atomicAdd(c.zs_tgt, 1ull); atomicAdd(c.zs_tgt_pc + rel, 1ull); }
+}
+
 struct RecallAccParams {
     const int* out_pair; const int* out_pred; const int* out_sub; const int* out_obj;      // [n_img][K] ranked lists
     const int* out_count; int K, n_img;                                                    // [n_img]
@@ -17,11 +46,8 @@ struct RecallAccParams {
     const int* sub_idx; const int* obj_idx; const int* image; const int* directed;         // [P]
     const unsigned char* included; int P;                   // [P] kept steps or NULL
     const int* img_targets;                                 // [n_img] connected targets of the kept steps per image (Top-3)
-    int ks[METRIC_MAX_KS]; int n_k;
-    const unsigned* zs; int C, R;                           // zero-shot bitmap (triplet_bit's layout) or NULL
     int F; double iou_thresh;
-    unsigned long long* hits; unsigned long long* hits_pc; unsigned long long* tgt; unsigned long long* tgt_pc;              // [n_k], [n_k][R], [1], [R]
-    unsigned long long* zs_hits; unsigned long long* zs_hits_pc; unsigned long long* zs_tgt; unsigned long long* zs_tgt_pc;  // the zero-shot twins
+    RecallCounters c;
 };
 
 // One wavefront per pair row; rows that are no connected target of a kept step leave at once.  The scan is first_match_rank
@@ -53,22 +79,52 @@ __global__ __launch_bounds__(256) void recall_accumulate_kernel(const RecallAccP
         return pred && box_iou_ok(tsb, load_box(p.boxes, cs, p.F), p.iou_thresh) &&
                box_iou_ok(tob, load_box(p.boxes, co, p.F), p.iou_thresh);
     });
-    if (lane != 0) return;
-    const bool cls = rel >= 0 && rel < p.R;
-    const bool zs = p.zs && triplet_bit(p.zs, sc, rel, oc, p.C, p.R);
-    const int n_t = p.n_pred == 3 ? p.img_targets[img] : 0;
-    for (int i = 0; i < p.n_k; ++i) {
-        // evaluator.py:435 `hit < k and hit < count`; Top-3 :668 `hit < count and hit < max(k, targets of the image)`
-        const int bound = p.n_pred == 3 ? max(p.ks[i], n_t) : p.ks[i];
-        if (hit < cnt && hit < bound) {
-            atomicAdd(p.hits + i, 1ull);
-            if (cls) atomicAdd(p.hits_pc + (long)i * p.R + rel, 1ull);
-            if (zs) { atomicAdd(p.zs_hits + i, 1ull); atomicAdd(p.zs_hits_pc + (long)i * p.R + rel, 1ull); }
+    if (lane == 0) count_target(p.c, sc, rel, oc, hit, cnt, p.n_pred == 3 ? p.img_targets[img] : -1);
+}
+
+// SGDET / SGCLS (evaluator.py:272-277, 306-356 with predcls=False): the targets are ground-truth triples of their own - image,
+// predicate, classes and boxes per row of a target table (pairs.sg_target_table) - and the candidates are the ranked pairs of the
+// PREDICTED objects; labels match by equality or through the reference's equivalence classes (utils.py:355-373, `equiv`
+// [n_equiv][n_equiv] u8 or NULL).  The target table's box rows carry no alignment promise (four-load load_box); `boxes` is the
+// scene's 16-byte aligned table.
+struct RecallTgtParams {
+    const int* out_pred; const int* out_sub; const int* out_obj; const int* out_count; int K, n_img;
+    const long* cats; const float* boxes; int n_obj;
+    const int* t_image; const long* t_rel; const long* t_scat; const long* t_ocat; const float* t_sbox; const float* t_obox; int n_t;
+    const unsigned char* equiv; int n_equiv;
+    int F; double iou_thresh;
+    RecallCounters c;
+};
+
+// One wavefront per row of the target table.  A row with predicate -1, with an image out of range or with an image that owns no
+// candidate leaves at once and is not counted as a target: Evaluator.compute visits the images of the candidates only.  The scan
+// and the test are recall_hits_kernel's with one predicate per candidate.
+__global__ __launch_bounds__(256) void recall_accumulate_targets_kernel(const RecallTgtParams p) {
+    const int lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (t >= p.n_t) return;
+    const long rel = p.t_rel[t];
+    const int img = p.t_image[t];
+    if (rel == -1 || img < 0 || img >= p.n_img) return;
+    const int cnt = min(p.out_count[img], p.K);
+    if (cnt <= 0) return;
+    const long sc = p.t_scat[t], oc = p.t_ocat[t];
+    const GridBox tsb = load_box(p.t_sbox + 4L * t, p.F), tob = load_box(p.t_obox + 4L * t, p.F);
+    const bool t_in = sc >= 0 && sc < p.n_equiv && oc >= 0 && oc < p.n_equiv;
+    const int hit = first_match_rank(cnt, p.K, [&](int j) {
+        const long o = (long)img * p.K + j;
+        const int cs = p.out_sub[o], co = p.out_obj[o];
+        if (!(cs >= 0 && cs < p.n_obj && co >= 0 && co < p.n_obj)) return false;
+        const long csc = p.cats[cs], coc = p.cats[co];
+        bool label = csc == sc && coc == oc;
+        if (p.equiv && !label) {
+            const bool in = t_in && csc >= 0 && csc < p.n_equiv && coc >= 0 && coc < p.n_equiv;
+            label = in && p.equiv[sc * p.n_equiv + csc] && p.equiv[oc * p.n_equiv + coc];
         }
-    }
-    atomicAdd(p.tgt, 1ull);
-    if (cls) atomicAdd(p.tgt_pc + rel, 1ull);
-    if (zs) { atomicAdd(p.zs_tgt, 1ull); atomicAdd(p.zs_tgt_pc + rel, 1ull); }
+        return label && p.out_pred[o] == rel && box_iou_ok(tsb, load_box(p.boxes, cs, p.F), p.iou_thresh) &&
+               box_iou_ok(tob, load_box(p.boxes, co, p.F), p.iou_thresh);
+    });
+    if (lane == 0) count_target(p.c, sc, rel, oc, hit, cnt, -1);
 }
 
 struct PrecisionAccParams {
@@ -130,13 +186,35 @@ int sgc_recall_accumulate(const int* out_pair, const int* out_pred, const int* o
     if (!out_pred || !out_sub || !out_obj || !out_count || !cats || !boxes || !sub_idx || !obj_idx || !image || !directed || !hits ||
         !hits_pc || !targets || !targets_pc)
         return SGC_ERR_ARG;
-    typedef unsigned long long u64;
     RecallAccParams p{out_pair, out_pred, out_sub, out_obj, out_count, K, n_img, cand_pred, n_pred, cats, boxes, n_obj, sub_idx, obj_idx,
-                      image, directed, included, n_pairs, img_targets, {0}, n_k, zero_shot, C, R, feature_size, iou_thresh,
-                      (u64*)hits, (u64*)hits_pc, (u64*)targets, (u64*)targets_pc, (u64*)zs_hits, (u64*)zs_hits_pc, (u64*)zs_targets,
-                      (u64*)zs_targets_pc};
-    for (int i = 0; i < n_k; ++i) p.ks[i] = top_k[i];                  // top_k is a HOST array
+                      image, directed, included, n_pairs, img_targets, feature_size, iou_thresh,
+                      {{0}, n_k, zero_shot, C, R, (u64*)hits, (u64*)hits_pc, (u64*)targets, (u64*)targets_pc, (u64*)zs_hits,
+                       (u64*)zs_hits_pc, (u64*)zs_targets, (u64*)zs_targets_pc}};
+    for (int i = 0; i < n_k; ++i) p.c.ks[i] = top_k[i];                // top_k is a HOST array
     SGC_LAUNCH(recall_accumulate_kernel, dim3((n_pairs + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
+int sgc_recall_accumulate_targets(const int* out_pred, const int* out_sub, const int* out_obj, const int* out_count, int n_img, int K,
+                                  const long* cats, const float* boxes, int n_obj, const int* t_image, const long* t_rel,
+                                  const long* t_scat, const long* t_ocat, const float* t_sbox, const float* t_obox, int n_targets,
+                                  const unsigned char* equiv, int n_equiv, const int* top_k, int n_k, const unsigned* zero_shot, int C,
+                                  int R, int feature_size, double iou_thresh, long* hits, long* hits_pc, long* targets,
+                                  long* targets_pc, long* zs_hits, long* zs_hits_pc, long* zs_targets, long* zs_targets_pc,
+                                  void* stream) {
+    if (K < 1 || K > 128 || n_k < 1 || n_k > METRIC_MAX_KS || !top_k || R < 1 || (equiv && n_equiv < 1)) return SGC_ERR_ARG;
+    if (zero_shot && (C < 1 || !zs_hits || !zs_hits_pc || !zs_targets || !zs_targets_pc)) return SGC_ERR_ARG;
+    if (n_targets <= 0 || n_img <= 0) return SGC_OK;
+    if (!out_pred || !out_sub || !out_obj || !out_count || !cats || !boxes || !t_image || !t_rel || !t_scat || !t_ocat || !t_sbox ||
+        !t_obox || !hits || !hits_pc || !targets || !targets_pc)
+        return SGC_ERR_ARG;
+    RecallTgtParams p{out_pred, out_sub, out_obj, out_count, K, n_img, cats, boxes, n_obj, t_image, t_rel, t_scat, t_ocat, t_sbox, t_obox,
+                      n_targets, equiv, equiv ? n_equiv : 0, feature_size, iou_thresh,
+                      {{0}, n_k, zero_shot, C, R, (u64*)hits, (u64*)hits_pc, (u64*)targets, (u64*)targets_pc, (u64*)zs_hits,
+                       (u64*)zs_hits_pc, (u64*)zs_targets, (u64*)zs_targets_pc}};
+    for (int i = 0; i < n_k; ++i) p.c.ks[i] = top_k[i];                // top_k is a HOST array
+    SGC_LAUNCH(recall_accumulate_targets_kernel, dim3((n_targets + 3) / 4), dim3(256), 0, (hipStream_t)stream, p);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }
@@ -150,7 +228,6 @@ int sgc_precision_accumulate(const int* out_pred, const int* out_sub, const int*
     if (!out_pred || !out_sub || !out_obj || !out_count || !image_ptr || !cats || !boxes || !sub_idx || !obj_idx || !directed || !ap ||
         !ap_union || !num_ap)
         return SGC_ERR_ARG;
-    typedef unsigned long long u64;
     PrecisionAccParams p{out_pred, out_sub, out_obj, out_count, K, n_img, n_rank, image_ptr, pair_list, cats, boxes, n_obj, sub_idx,
                          obj_idx, directed, included, n_pairs, R, feature_size, iou_thresh, (u64*)ap, (u64*)ap_union, (u64*)num_ap};
     const long waves = (long)n_img * n_rank;

@@ -25,7 +25,8 @@ import torch.distributed as dist
 from .evaluator import Evaluator, Evaluator_Top3
 from .object_frontend import DetrFrontEnd
 from .metrics import RecallMeter
-from .pair_loop import MinibatchLookahead, evaluate_minibatch, evaluate_sgdet_minibatch, freeze_setup_objects, score_minibatch
+from .pair_loop import (MinibatchLookahead, evaluate_minibatch, evaluate_sgdet_minibatch, freeze_setup_objects, score_minibatch,
+                        score_sgdet_minibatch)
 from .pairs import flatten_scene
 from .train_test import (_collate, _host, _record_test, _to_batch, build_classifier, build_feature_encoder, load_checkpoint, setup)
 from .train_utils import process_image_features
@@ -191,9 +192,17 @@ def _detr_outputs(detr, image2, rank):
 
 
 def _sg_common(gpu, args, test_subset, sgcls: bool):
+    """``eval_sgd`` / ``eval_sgc``.  With ``args['training']['device_metrics']`` the ``Evaluator`` is replaced by one
+    ``metrics.RecallMeter``: ``pair_loop.score_sgdet_minibatch`` updates its device counters per minibatch from the ground truth as one
+    target table, and the host reads them only where a record is written; records and return values are the same."""
     T = args["training"]
     rank, loader, model, detr = _start(gpu, args, test_subset)
-    Recall = Evaluator(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100])
+    meter = Recall = None
+    if T.get("device_metrics"):
+        meter = RecallMeter(args, args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100],
+                            device=next(model.parameters()).device)
+    else:
+        Recall = Evaluator(args=args, num_classes=args["models"]["num_relations"], iou_thresh=0.5, top_k=[20, 50, 100])
     sub2super = torch.load(args["dataset"]["sub2super_cat_dict"])
     try:
         from dataset_utils import object_class_alp2fre                # the host repository's own class-index table
@@ -208,6 +217,7 @@ def _sg_common(gpu, args, test_subset, sgcls: bool):
     record_test = _host("record_test_results", _record_test)
     test_record = []
     recall = mean_recall = recall_zs = mean_recall_zs = None
+    unread = False
     name = "SGC" if sgcls else "SGD"
     print("Start Testing %s..." % name)
     freeze_setup_objects()
@@ -232,14 +242,26 @@ def _sg_common(gpu, args, test_subset, sgcls: bool):
                 categories_pred, cat_conf, bbox_pred = matched[0], matched[1], matched[2]
             last = batch_count + 1 == len(loader)
             if batch_count % T["eval_freq_test"] == 0 or last:
-                evaluate_sgdet_minibatch(model, image_feature, depth, categories_pred, cat_conf, bbox_pred, Recall, sub2super=sub2super,
-                                         targets=(relationships, subj_or_obj, cats_t, box_t),
-                                         skip_filtered=bool(T.get("skip_filtered_pairs", False)))
-                recall, _, mean_recall, recall_zs, _, mean_recall_zs = Recall.compute(per_class=True, predcls=False)
-                Recall.clear_data()
-                if batch_count % T["print_freq_test"] == 0 or last:
+                write = batch_count % T["print_freq_test"] == 0 or last
+                if meter is not None:
+                    # the target table is built on the host: the loader's own (host) class and box lists, not their device copies
+                    score_sgdet_minibatch(model, image_feature, depth, categories_pred, cat_conf, bbox_pred, meter, sub2super=sub2super,
+                                          targets=(relationships, subj_or_obj, categories_target, bbox_target),
+                                          skip_filtered=bool(T.get("skip_filtered_pairs", False)))
+                    unread = not write
+                    if write:               # the meter's host read: only where a record is written
+                        recall, _, mean_recall, recall_zs, _, mean_recall_zs = meter.compute(per_class=True)
+                else:
+                    evaluate_sgdet_minibatch(model, image_feature, depth, categories_pred, cat_conf, bbox_pred, Recall,
+                                             sub2super=sub2super, targets=(relationships, subj_or_obj, cats_t, box_t),
+                                             skip_filtered=bool(T.get("skip_filtered_pairs", False)))
+                    recall, _, mean_recall, recall_zs, _, mean_recall_zs = Recall.compute(per_class=True, predcls=False)
+                    Recall.clear_data()
+                if write:
                     record_test(args, test_record, rank, T["test_epoch"], None, recall, None, mean_recall, recall_zs, mean_recall_zs,
                                 torch.tensor(0.0), 0.0, 0.0, torch.tensor(0.0), 0.0, None, None)
+    if unread:                              # minibatches scored after the last record: the return value counts them, as the evaluator's does
+        recall, _, mean_recall, _, _, _ = meter.compute(per_class=True)
     _finish(name)
     return recall, mean_recall
 

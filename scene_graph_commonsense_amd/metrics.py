@@ -15,8 +15,11 @@ outputs and the scene's tables in place:
 the evaluators' formulas, NaN handling included.  The counters run on across ``update`` calls as the evaluators' run on across
 ``clear_data()``; integer sums are order-independent, so two runs give identical bits.
 
-PredCLS only: SGDET / SGCLS (label-equivalence table, per-image target lists through ``accumulate_target``) stay on the
-``Evaluator``.  There is no CPU path: tensors must live on the GPU.
+SGDET / SGCLS (``evaluator.py:272-277, 306-356`` with ``predcls=False``): the targets are ground-truth triples with classes and boxes
+of their own, the candidates live on the PREDICTED objects' pair rows, and labels match through the reference's equivalence classes
+(``utils.py:355-373``).  ``update(sg_targets=..., cat_conf=...)`` takes them as one device table (``pairs.sg_target_table``) and counts
+with ``sgc_recall_accumulate_targets`` (one wavefront per ground-truth triple); only the Recall@K and zero-shot counters move, as in
+the reference's ``eval_sgd`` / ``eval_sgc``.  There is no CPU path: tensors must live on the GPU.
 """
 from __future__ import annotations
 
@@ -41,6 +44,12 @@ def parse_triplet_keys(keys):
     for k in keys:
         out.append(tuple(int(v) for v in k.split("_")) if isinstance(k, str) else tuple(int(v) for v in k))
     return out
+
+
+def upload_sg_targets(table, dev):
+    """``pairs.sg_target_table``'s numpy arrays as the device tensors ``RecallMeter.update(sg_targets=...)`` takes."""
+    dtypes = (np.int32, np.int64, np.int64, np.int64, np.float32, np.float32)
+    return tuple(torch.from_numpy(np.ascontiguousarray(a, dtype=d)).to(dev) for a, d in zip(table, dtypes))
 
 
 def scene_boxes(scene, dev) -> torch.Tensor:
@@ -87,6 +96,7 @@ class RecallMeter:
         for part in ("ap", "ap_union", "num_ap"):
             self._layout["precision." + part] = (o, R, (R,))
             o += R
+        self._equiv = None                  # [160,160] u8 device copy of evaluator._equiv_matrix(), uploaded at the first SGDET / SGCLS update
         self.zero_shot = None               # [C*R*C bits] device bitmap of the zero-shot triplets (TripletBitmaps' layout)
         self._cs_keys, self._cs = None, None
         if self.dataset == "vg":
@@ -121,18 +131,33 @@ class RecallMeter:
 
     # ------------------------------------------------------------------ update
     def update(self, scene, out, overlap: Optional[torch.Tensor] = None, included: Optional[torch.Tensor] = None, commonsense=None,
-               top3: bool = True, directed: Optional[torch.Tensor] = None):
+               top3: bool = True, directed: Optional[torch.Tensor] = None, *, sg_targets=None, cat_conf: Optional[torch.Tensor] = None):
         """Add one minibatch: ``scene`` (``pairs.DeviceScene`` with relation targets, or ``directed`` [P] given), ``out`` the forward's
         ``PairOutputs``, ``overlap`` [P] u8 the overlap mask (0 -> the pair's candidates rank at -inf), ``included`` [P] the pairs of the
         kept direction-steps (others are neither candidates nor targets), ``commonsense`` a ``commonsense.TripletBitmaps`` (default: the
         sets of ``args`` in run modes train_cs / eval_cs).  ``top3``: also the Top-3 counters, for a hierarchical head.  With
         ``dataset == 'oiv6'`` the precision counters are updated from the first 20 ranks of the same ranking - what ``compute()``
-        followed by ``compute_precision()`` ranks.  No host synchronisation."""
-        from .pair_loop import image_pair_lists
+        followed by ``compute_precision()`` ranks.  No host synchronisation.
+        ``cat_conf`` [P] f32: subject + object category confidence of every pair row, added to each of its candidates before the
+        connectivity term (``Evaluator.accumulate_candidates(cat_confidence=...)``).
+        ``sg_targets``: SGDET / SGCLS - the ground truth as a device table (image int32 [T], relation, subject class, object class
+        int64 [T], subject box, object box f32 [T,4]: ``upload_sg_targets(pairs.sg_target_table(...))``) instead of ``directed``; the
+        scene is then the PREDICTED objects' and labels match through the reference's equivalence classes.  Only ``recall.*`` and
+        ``zero_shot.*`` move (``eval_sgd`` / ``eval_sgc`` record neither Top-3 nor wmAP)."""
         if not torch.is_tensor(out.cand_conf) or not out.cand_conf.is_cuda:
             raise RuntimeError("RecallMeter.update runs on the GPU (sgc_recall_accumulate, no CPU fallback): the forward's outputs must "
                                "be cuda tensors")
         dev = out.cand_conf.device
+        if cat_conf is not None:
+            if not torch.is_tensor(cat_conf) or not cat_conf.is_cuda:
+                raise RuntimeError("RecallMeter.update runs on the GPU (no CPU fallback): cat_conf must be a cuda tensor")
+            if int(cat_conf.numel()) != int(scene.n_pairs):
+                raise ValueError("cat_conf must hold one value per pair row")
+            cat_conf = cat_conf.to(torch.float32).contiguous()
+        if sg_targets is not None:
+            if directed is not None:
+                raise ValueError("sg_targets and directed are two ways to give the ground truth: pass one of them")
+            return self._update_sg(scene, out, overlap, included, commonsense, sg_targets, cat_conf, dev)
         directed = scene.directed if directed is None else directed
         if directed is None:
             raise ValueError("the metrics need relation targets: flatten the scene from a batch with relationships / subj_or_obj")
@@ -142,17 +167,8 @@ class RecallMeter:
         if P == 0:
             return
         directed = directed.to(torch.int32).contiguous()
-        ptr, lst = image_pair_lists(scene)
-        B = int(ptr.numel()) - 1
-        boxes = scene_boxes(scene, dev)
-        if included is not None:
-            included = (included.view(torch.uint8) if included.dtype == torch.bool else included.to(torch.uint8)).contiguous()
-        K, R, n_k = self.top_k[-1], self.num_classes, len(self.top_k)
-        # torch's own log(sigmoid(x)), as the evaluator feed forms it: the ranked scores are bit for bit the evaluator's confidences
-        logsig = torch.log(torch.sigmoid(out.connectivity))
-        g = rank_scene_graphs(out.cand_conf, out.cand_pred, logsig, ptr, top_k=K, pair_list=lst, slot_major=False, mask=overlap,
-                              included=included, sub_idx=scene.sub_idx, obj_idx=scene.obj_idx, cats=scene.cats,
-                              bitmaps=self._bitmaps(commonsense))
+        g, ptr, lst, boxes, included, logsig = self._rank(scene, out, overlap, included, commonsense, cat_conf, dev)
+        B, K, R, n_k = int(ptr.numel()) - 1, self.top_k[-1], self.num_classes, len(self.top_k)
         lib = _lib.load()
         n_obj = int(scene.cats.numel())
         thr = ctypes.c_double(self.iou_thresh)
@@ -187,6 +203,54 @@ class RecallMeter:
                     is_target &= included.bool()
                 img_targets = torch.zeros(B, dtype=torch.int32, device=dev).index_add_(0, scene.image.long(), is_target.int())
                 accumulate(g3, "top3", cand_pred, 3, img_targets, None)
+
+    def _rank(self, scene, out, overlap, included, commonsense, cat_conf, dev):
+        """What every update starts with: the ranked lists of the minibatch's candidates (``sgc_scene_graph_topk``) and the tables they
+        were ranked from - (lists, image ptr, image pair list, raw boxes, included as u8, log-sigmoid connectivity)."""
+        from .pair_loop import image_pair_lists
+        ptr, lst = image_pair_lists(scene)
+        boxes = scene_boxes(scene, dev)
+        if included is not None:
+            included = (included.view(torch.uint8) if included.dtype == torch.bool else included.to(torch.uint8)).contiguous()
+        # torch's own log(sigmoid(x)), as the evaluator feed forms it: the ranked scores are bit for bit the evaluator's confidences
+        logsig = torch.log(torch.sigmoid(out.connectivity))
+        g = rank_scene_graphs(out.cand_conf, out.cand_pred, logsig, ptr, top_k=self.top_k[-1], pair_list=lst, slot_major=False,
+                              cat_conf=cat_conf, mask=overlap, included=included, sub_idx=scene.sub_idx, obj_idx=scene.obj_idx,
+                              cats=scene.cats, bitmaps=self._bitmaps(commonsense))
+        return g, ptr, lst, boxes, included, logsig
+
+    def _update_sg(self, scene, out, overlap, included, commonsense, sg_targets, cat_conf, dev):
+        from .evaluator import _equiv_matrix
+        if len(sg_targets) != 6:
+            raise ValueError("sg_targets is (image, relation, subject class, object class, subject box, object box)")
+        for t in sg_targets:
+            if not torch.is_tensor(t) or not t.is_cuda:
+                raise RuntimeError("RecallMeter.update runs on the GPU (sgc_recall_accumulate_targets, no CPU fallback): the target "
+                                   "table must be cuda tensors")
+        T = int(sg_targets[0].numel())
+        if any(int(t.numel()) != n * T for t, n in zip(sg_targets, (1, 1, 1, 1, 4, 4))):
+            raise ValueError("the arrays of sg_targets disagree in length: [T] image, relation and classes, [T,4] boxes")
+        P = int(scene.n_pairs)
+        if P == 0 or T == 0:
+            return
+        t_image = sg_targets[0].to(torch.int32).contiguous()
+        t_rel, t_scat, t_ocat = (t.to(torch.int64).contiguous() for t in sg_targets[1:4])
+        t_sbox, t_obox = (t.to(torch.float32).contiguous() for t in sg_targets[4:6])
+        if self._equiv is None:
+            self._equiv = torch.from_numpy(_equiv_matrix().astype(np.uint8)).to(self.device)
+        # (cand_conf + cat_conf) + log(sigmoid(connectivity)): bit for bit the evaluator's confidences with predcls=False
+        g, ptr, _, boxes, _, _ = self._rank(scene, out, overlap, included, commonsense, cat_conf, dev)
+        B, K, R, n_k = int(ptr.numel()) - 1, self.top_k[-1], self.num_classes, len(self.top_k)
+        v = lambda part: _lib.ptr(self.view("recall." + part))
+        z = (lambda part: _lib.ptr(self.view("zero_shot." + part))) if self.zero_shot is not None else (lambda part: _lib.ptr(None))
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().sgc_recall_accumulate_targets(
+                _lib.ptr(g.predicate), _lib.ptr(g.subject), _lib.ptr(g.object), _lib.ptr(g.count), B, K, _lib.ptr(scene.cats),
+                _lib.ptr(boxes), int(scene.cats.numel()), _lib.ptr(t_image), _lib.ptr(t_rel), _lib.ptr(t_scat), _lib.ptr(t_ocat),
+                _lib.ptr(t_sbox), _lib.ptr(t_obox), T, _lib.ptr(self._equiv), int(self._equiv.shape[0]), self._ks, n_k,
+                _lib.ptr(self.zero_shot), self.num_object_classes, R, self.feature_size, ctypes.c_double(self.iou_thresh), v("hits"),
+                v("hits_pc"), v("targets"), v("targets_pc"), z("hits"), z("hits_pc"), z("targets"), z("targets_pc"), _lib.stream_ptr()),
+                "sgc_recall_accumulate_targets")
 
     # ------------------------------------------------------------------ host reads
     def _host(self):

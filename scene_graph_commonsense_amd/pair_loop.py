@@ -313,16 +313,9 @@ def evaluate_minibatch(model, batch, evaluator=None, evaluator_top3=None, overla
     return scene, out, included.cpu().numpy(), directed_d.cpu().numpy().astype(np.int64)
 
 
-def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred, cat_pred_confidence, bbox_pred, evaluator,
-                             sub2super=None, targets=None, overlap_filtering: bool = True, skip_filtered: bool = False,
-                             workspace_budget: Optional[float] = None):
-    """SGDET evaluation of one minibatch (``evaluate.py:375-444``): every ordered pair of the PREDICTED objects of each image
-    (per-image lists as returned by ``object_frontend.DetrFrontEnd.sgdet``: categories, category confidences, boxes
-    (x0,x1,y0,y1) on the grid, one entry per image of ``image_feature``), overlap filter, evaluator fed in the reference's
-    candidate order with ``predcls=False`` semantics (category confidences added).  ``targets`` =
-    (relationships, subj_or_obj, categories_target, bbox_target) sets the ground truth through ``match_target_sgd`` +
-    ``Evaluator.accumulate_target``; call ``evaluator.compute(per_class, predcls=False)`` afterwards.
-    ``sub2super``: the ``sub2super_cat_dict`` (VG hierarchical label vectors)."""
+def _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super):
+    """(cfg, device, batch, scene): the ``SceneBatch`` and ``DeviceScene`` of the PREDICTED objects of one SGDET / SGCLS minibatch
+    (``evaluate.py:375-444``) - the batch construction ``evaluate_sgdet_minibatch`` and ``score_sgdet_minibatch`` share."""
     from .synthetic import SceneBatch
     cfg = model.head_config()
     dev = next(model.parameters()).device
@@ -335,15 +328,34 @@ def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred,
         sp = [[torch.as_tensor(sub2super[int(c)]) for c in cats.tolist()] for cats in categories_pred]
     batch = SceneBatch(image_feature, image_depth, [b.detach().float().cpu() for b in bbox_pred],
                        [c.detach().cpu().long() for c in categories_pred], sp, None, None)
-    scene = flatten_scene(cfg, batch, dev)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    select = _unfiltered_selection(scene, iou, (evaluator,)) if (skip_filtered and overlap_filtering) else None
+    return cfg, dev, batch, flatten_scene(cfg, batch, dev)
+
+
+def _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget):
+    """The fused forward over the predicted objects' pairs, in image groups when the minibatch exceeds the workspace budget."""
     groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))       # 16 images x 100+ detections: image groups
     if len(groups) > 1:
         out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
     else:
         out = model.forward_pairs(scene, iou_mask=iou, select=select)
     model.last_image_groups = groups
+    return out
+
+
+def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred, cat_pred_confidence, bbox_pred, evaluator,
+                             sub2super=None, targets=None, overlap_filtering: bool = True, skip_filtered: bool = False,
+                             workspace_budget: Optional[float] = None):
+    """SGDET evaluation of one minibatch (``evaluate.py:375-444``): every ordered pair of the PREDICTED objects of each image
+    (per-image lists as returned by ``object_frontend.DetrFrontEnd.sgdet``: categories, category confidences, boxes
+    (x0,x1,y0,y1) on the grid, one entry per image of ``image_feature``), overlap filter, evaluator fed in the reference's
+    candidate order with ``predcls=False`` semantics (category confidences added).  ``targets`` =
+    (relationships, subj_or_obj, categories_target, bbox_target) sets the ground truth through ``match_target_sgd`` +
+    ``Evaluator.accumulate_target``; call ``evaluator.compute(per_class, predcls=False)`` afterwards.
+    ``sub2super``: the ``sub2super_cat_dict`` (VG hierarchical label vectors)."""
+    cfg, dev, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
+    iou = overlap_mask(scene) if overlap_filtering else None
+    select = _unfiltered_selection(scene, iou, (evaluator,)) if (skip_filtered and overlap_filtering) else None
+    out = _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget)
     included, any_overlap = _step_filter(scene, iou)
     sel = torch.nonzero(included).flatten()
     sub, obj = scene.sub_idx.long()[sel], scene.obj_idx.long()[sel]
@@ -358,6 +370,38 @@ def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred,
         cs, co, bs, bo, rt = match_target_sgd(*targets)
         evaluator.accumulate_target(rt, cs, co, bs, bo)
     return scene, out, included.cpu().numpy()
+
+
+def score_sgdet_minibatch(model, image_feature, image_depth, categories_pred, cat_pred_confidence, bbox_pred, meter, sub2super=None,
+                          targets=None, overlap_filtering: bool = True, skip_filtered: bool = False,
+                          workspace_budget: Optional[float] = None):
+    """``evaluate_sgdet_minibatch`` for a ``metrics.RecallMeter``: SGDET / SGCLS Recall@K and zero-shot recall as device counters,
+    without the appended int64 copies of every candidate, without ``match_target_sgd``'s per-element lists and without a read-back.
+    The arguments are ``evaluate_sgdet_minibatch``'s; ``targets`` = (relationships, subj_or_obj, categories_target, bbox_target) is
+    required (a meter without targets measures nothing).  The ground truth becomes one table (``pairs.sg_target_table``); it, the
+    per-pair category confidences, the image lists and the boxes are put on the device BEFORE the forward is enqueued, and after
+    it only ``meter.update(sg_targets=..., cat_conf=...)`` runs - nothing synchronises with the host; the numbers are the caller's
+    ``meter.compute(per_class)``, the 6-tuple of ``Evaluator.compute(per_class, predcls=False)``.  Sets ``model.last_outputs``.
+    Returns (scene, outputs)."""
+    from .metrics import scene_boxes, upload_sg_targets
+    from .pairs import sg_target_table
+    if targets is None:
+        raise ValueError("the metrics need the ground truth: targets=(relationships, subj_or_obj, categories_target, bbox_target)")
+    cfg, dev, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
+    table = upload_sg_targets(sg_target_table(*targets), dev)
+    conf_obj = torch.cat([torch.as_tensor(c).reshape(-1).to(dev, torch.float32) for c in cat_pred_confidence])
+    if int(conf_obj.numel()) != int(scene.cats.numel()):
+        raise ValueError("cat_pred_confidence must hold one value per predicted object")
+    cat_conf = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+    image_pair_lists(scene)                         # the per-scene tables of the update, made (and uploaded) once, before the forward
+    scene_boxes(scene, dev)
+    iou = overlap_mask(scene) if overlap_filtering else None
+    included = _step_filter(scene, iou)[0] if overlap_filtering else None
+    select = _unfiltered_selection(scene, iou, (meter,)) if (skip_filtered and overlap_filtering) else None
+    out = _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget)
+    model.last_outputs = out
+    meter.update(scene, out, overlap=iou, included=included, sg_targets=table, cat_conf=cat_conf)
+    return scene, out
 
 
 def image_pair_lists(scene: DeviceScene):
@@ -428,7 +472,7 @@ def score_minibatch(model, batch, meter, overlap_filtering: bool = True, scene: 
     as ``predict_scene_graphs`` (default: the meter's own sets in run mode eval_cs).  Sets ``model.last_outputs`` and, when the scene has
     raw targets and nothing was skipped, ``model.last_connectivity_stats``.  Everything the update needs besides the forward's outputs
     is put on the device BEFORE the forward is enqueued; nothing after it synchronises with the host - the numbers are the caller's
-    ``meter.compute*()``.  PredCLS only: SGDET / SGCLS stay on ``evaluate_sgdet_minibatch`` and the ``Evaluator``.
+    ``meter.compute*()``.  PredCLS; the SGDET / SGCLS counterpart is ``score_sgdet_minibatch``.
     Returns (scene, outputs)."""
     from .commonsense import TripletBitmaps
     from .metrics import scene_boxes

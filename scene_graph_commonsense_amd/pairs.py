@@ -428,3 +428,46 @@ def match_target_sgd(relationships, subj_or_obj, categories_target, bbox_target)
         for lst, v in zip(out, vals):
             lst.append(v)
     return out
+
+
+def _host_array(x):
+    return x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+
+
+def _triangle(rows, G: int) -> np.ndarray:
+    """Entries [:g] of rows[g-1] for g = 1 .. G-1, concatenated.  The loaders' rows are 1-d tensors of exactly g entries: one
+    ``torch.cat``; anything else is sliced row by row."""
+    rows = rows[:G - 1]
+    if all(torch.is_tensor(r) and r.dim() == 1 and int(r.shape[0]) == g for g, r in enumerate(rows, start=1)):
+        return torch.cat(list(rows)).detach().cpu().numpy()
+    return np.concatenate([_host_array(r).reshape(-1)[:g] for g, r in enumerate(rows, start=1)])
+
+
+def sg_target_table(relationships, subj_or_obj, categories_target, bbox_target):
+    """The ground-truth triples of a minibatch as ONE table for ``sgc_recall_accumulate_targets`` (``metrics.RecallMeter.update(
+    sg_targets=...)``): numpy arrays (image int32 [T], relation int64 [T], subject class int64 [T], object class int64 [T], subject box
+    f32 [T,4], object box f32 [T,4]).  The rows are ``match_target_sgd``'s per-image lists concatenated in image order - images
+    without relations contribute none - with its loop bound (``utils.py:294-350``: relations whose graph object is the last object of
+    an image are not collected).  One pass of array operations per image, no per-element appends."""
+    host = _host_array
+    parts = ([], [], [], [], [], [])
+    for b in range(len(relationships)):
+        G = len(relationships[b])                    # graph objects 1 .. G-1 (the reference's bound; the image has G+1 objects)
+        if G < 2:
+            continue
+        flag, rel = _triangle(subj_or_obj[b], G), _triangle(relationships[b], G).astype(np.int64)
+        width = np.arange(1, G)
+        g_of = np.repeat(width, width)
+        e_of = np.arange(g_of.size) - np.repeat(np.cumsum(width) - width, width)
+        keep = np.nonzero((flag == 1) | (flag == 0))[0]
+        if keep.size == 0:
+            continue
+        first = flag[keep] == 1                      # 1: the graph object is the subject (utils.py:316-331)
+        s_i, o_i = np.where(first, g_of[keep], e_of[keep]), np.where(first, e_of[keep], g_of[keep])
+        cats = host(categories_target[b]).reshape(-1).astype(np.int64)
+        box = host(bbox_target[b]).reshape(-1, 4).astype(np.float32)
+        for lst, v in zip(parts, (np.full(keep.size, b, dtype=np.int32), rel[keep], cats[s_i], cats[o_i], box[s_i], box[o_i])):
+            lst.append(v)
+    empty = (np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 4), np.float32),
+             np.zeros((0, 4), np.float32))
+    return tuple(np.concatenate(p) if p else e for p, e in zip(parts, empty))
