@@ -359,6 +359,37 @@ int sgc_bayes_head_any_loss_bwd(const float* h, const float* W, const float* dz,
  * sgc_bayes_head_any, so cand_conf [M][3] is bit for bit the block maxima of its rel; cand_pred [M][3] int32, sup [M][3]. */
 int sgc_bayes_head_any_candidates(const float* h, const float* W, const float* bias, int M, int D, int ng, int np, int ns, float T1,
                                   float T2, float T3, float* cand_conf, int* cand_pred, float* sup, void* stream);
+/* The commonsense penalty of run_mode train_cs fused into the plug-and-play head's loss   (train_utils.py:36-60, hierarchical branch:
+ * three max-softmax values and arg-maxes per row, a host round trip and two dict lookups per candidate, two masked means; plus the
+ * loss of sgc_bayes_head_any_loss, which it extends: same arguments, same NLL bits).  One call = one classifier call of the reference.
+ * subject_cat / object_cat [M] int64 (cat_is_int64 != 0) or int32; aligned / violated: sgc_commonsense_filter's bitmaps over
+ * C x R x C with R = ng + np + ns.  Candidate (m, k) is (subject_cat[m], pred[m][k], object_cat[m]) with pred the cand_pred of
+ * sgc_bayes_head_any_candidates; weak = not aligned, strong = violated, a label out of range is in neither set.  With
+ * p = max softmax(z_k / T_k): penalty = [N_w > 0] lambda_weak sum(weak p) / N_w + [N_s > 0] lambda_strong sum(strong p) / N_s over
+ * all rows, with or without a relation target.  target may be NULL (then norm and dz are unused): the penalty alone.
+ * dz [M][64] as there; dir [M][64] (out) = p ([j == pred] - softmax_j) / T_k on the fine rows, 0 elsewhere: dp/dz without the
+ * normaliser; flags [M][3] u8 (out): bit 0 weak, bit 1 strong; dz, dir + flags may be NULL when no gradient is wanted.
+ * part [3 ceil(M/32)] double and cnt_part [2 ceil(M/32)] int: scratch (per-workgroup partials, summed in a fixed order).
+ * out [5] = {nll + lambda_cs penalty, nll, penalty, lambda_cs lambda_weak / N_w, lambda_cs lambda_strong / N_s} (the last two 0
+ * where the count is 0: the backward's coefficients); counts [2] int64 = {N_w, N_s}.  Nothing waits for the device. */
+int sgc_bayes_head_any_loss_cs(const float* h, const float* W, const float* bias, const void* target, int target_is_int64,
+                               const float* class_weight, const void* subject_cat, const void* object_cat, int cat_is_int64,
+                               const unsigned* aligned, const unsigned* violated, int C, int M, int D, int ng, int np, int ns, float T1,
+                               float T2, float T3, float lambda_cs, float lambda_weak, float lambda_strong, float* norm, float* dz,
+                               float* dir, unsigned char* flags, double* part, int* cnt_part, float* out, long long* counts,
+                               void* stream);
+/* Its backward (autograd of train_utils.py:56-60 and :131-157 through model.py:24-34; the arg-max is a constant): the second stage of
+ * sgc_bayes_head_any_bwd fed g[0] (dz + c dir), c = coef[0] on a weak block + coef[1] on a strong block, coef = out + 3 of the
+ * forward.  dz may be NULL (= zero).  dh, part as in sgc_bayes_head_any_loss_bwd. */
+int sgc_bayes_head_any_loss_cs_bwd(const float* h, const float* W, const float* dz, const float* dir, const unsigned char* flags,
+                                   const float* coef, const float* g, int M, int D, int ng, int np, int ns, float* dh, float* part,
+                                   void* stream);
+/* sgc_bayes_head_any_candidates with the filter of run_mode eval_cs on every slot   (evaluator.py:189-194: confidence = -inf where
+ * the triplet (subject_cat[m], cand_pred[m][k], object_cat[m]) is violated or not aligned; the predicates stay). */
+int sgc_bayes_head_any_candidates_cs(const float* h, const float* W, const float* bias, const void* subject_cat, const void* object_cat,
+                                     int cat_is_int64, const unsigned* aligned, const unsigned* violated, int C, int M, int D, int ng,
+                                     int np, int ns, float T1, float T2, float T3, float* cand_conf, int* cand_pred, float* sup,
+                                     void* stream);
 
 /* Per-image stable descending top-K over the accumulated candidates   (evaluator.py:292-316: confidence += connectivity, argsort, top 100).
  * conf [n_cand] f32 (already including the connectivity term), seg_ptr [n_img+1]; out_idx [n_img][K] image-local candidate

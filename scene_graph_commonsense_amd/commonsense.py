@@ -36,6 +36,22 @@ class TripletBitmaps:
         words = (bits.reshape(nwords, 32) << np.arange(32, dtype=np.uint64)).sum(axis=1).astype(np.uint32)   # bit b of word w
         return torch.from_numpy(words.view(np.int32).copy()).to(self.device)
 
+    @classmethod
+    def from_masks(cls, aligned, violated, device) -> "TripletBitmaps":
+        """The bitmaps of two dense bool arrays [C, R, C] (entry [s, r, o] = the triplet is in the set) - the same layout as
+        ``_pack`` without a Python loop over the keys."""
+        aligned, violated = (np.ascontiguousarray(np.asarray(m.cpu() if torch.is_tensor(m) else m, dtype=bool)) for m in (aligned, violated))
+        if aligned.ndim != 3 or aligned.shape[0] != aligned.shape[2] or violated.shape != aligned.shape:
+            raise ValueError("aligned and violated must be bool [C, R, C] of one shape")
+        self = cls((), (), aligned.shape[0], aligned.shape[1], device)
+
+        def pack(mask):
+            bits = mask.reshape(-1)
+            bits = np.concatenate((bits, np.zeros(-bits.size % 32, dtype=bool)))
+            return torch.from_numpy(np.packbits(bits, bitorder="little").view("<u4").view(np.int32).copy()).to(self.device)
+        self.aligned, self.violated = pack(aligned), pack(violated)
+        return self
+
     def filter_(self, subject_cat: torch.Tensor, relation_pred: torch.Tensor, object_cat: torch.Tensor,
                 confidence: torch.Tensor) -> torch.Tensor:
         """confidence[i] = -inf where the triplet is violated or not aligned (in place, GPU only)."""

@@ -693,6 +693,70 @@ class _BayesHeadLossFunction(torch.autograd.Function):
         return (dh, *grads, None, None, None)
 
 
+class _BayesHeadCommonsenseFunction(torch.autograd.Function):
+    """``hierarchical_nll(..., commonsense=)`` and ``commonsense_penalty`` as ONE autograd node: forward =
+    ``sgc_bayes_head_any_loss_cs`` (the loss forward with the penalty of ``train_utils.py:36-60`` in the same epilogue; keeps dz, the
+    un-normalised penalty direction, the flags and the two coefficients), backward = ``sgc_bayes_head_any_loss_cs_bwd`` + the
+    fixed-order partial sum.  Nothing here waits for the device.  Inputs as ``_BayesHeadLossFunction`` (target None = the penalty
+    alone), then subject_cat / object_cat [M] (int64 / int32, contiguous), the TripletBitmaps and the three lambdas.  Returns
+    nll + lambda_commonsense * penalty; ``head.last_loss_terms`` / ``head.last_cs_counts`` hold the parts."""
+
+    @staticmethod
+    def forward(ctx, h, w1, b1, w2, b2, w3, b3, w5, b5, head, target, class_weight, scat, ocat, cs, lam, lam_weak, lam_strong):
+        W, b = head._packed(h.device)
+        M, D = h.shape
+        dev = h.device
+        lib = _lib.load()
+        need = any(ctx.needs_input_grad[:9])
+        norm = torch.empty(4, dtype=torch.float32, device=dev) if target is not None else None
+        out = torch.empty(5, dtype=torch.float32, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        dz = torch.empty(M, 64, dtype=torch.float32, device=dev) if need and target is not None else None
+        dirv = torch.empty(M, 64, dtype=torch.float32, device=dev) if need else None
+        flags = torch.empty(M, 3, dtype=torch.uint8, device=dev) if need else None
+        n32 = (M + 31) // 32
+        part = torch.empty(3 * n32, dtype=torch.float64, device=dev)
+        cnt_part = torch.empty(2 * n32, dtype=torch.int32, device=dev)
+        f = ctypes.c_float
+        _lib.check(lib.sgc_bayes_head_any_loss_cs(
+            _lib.ptr(h), _lib.ptr(W), _lib.ptr(b), _lib.ptr(target), int(target is not None and target.dtype == torch.int64),
+            _lib.ptr(class_weight), _lib.ptr(scat), _lib.ptr(ocat), int(scat.dtype == torch.int64), _lib.ptr(cs.aligned),
+            _lib.ptr(cs.violated), cs.C, M, D, head.ng, head.np_, head.ns, f(head.T1), f(head.T2), f(head.T3), f(lam), f(lam_weak),
+            f(lam_strong), _lib.ptr(norm), _lib.ptr(dz), _lib.ptr(dirv), _lib.ptr(flags), _lib.ptr(part), _lib.ptr(cnt_part),
+            _lib.ptr(out), _lib.ptr(counts), _lib.stream_ptr()), "sgc_bayes_head_any_loss_cs")
+        if need:
+            ctx.save_for_backward(h, W, dirv, flags, out, *(() if dz is None else (dz,)))
+        ctx.head = head
+        head.last_loss_terms = (out[1], out[2])
+        head.last_cs_counts = counts
+        return out[0].clone()
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        h, W, dirv, flags, out = ctx.saved_tensors[:5]
+        dz = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else None
+        head = ctx.head
+        need_h, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[1:9])
+        M, D = h.shape
+        lib = _lib.load()
+        g = g.to(torch.float32).contiguous()
+        dh = torch.empty_like(h) if need_h else None
+        n_part = (M + HEAD_ANY_ROWS - 1) // HEAD_ANY_ROWS
+        part = torch.empty(n_part, 64, D + 1, dtype=torch.float32, device=h.device) if need_w else None
+        _lib.check(lib.sgc_bayes_head_any_loss_cs_bwd(_lib.ptr(h), _lib.ptr(W), _lib.ptr(dz), _lib.ptr(dirv), _lib.ptr(flags),
+                                                      ctypes.c_void_p(out.data_ptr() + 12), _lib.ptr(g), M, D, head.ng, head.np_,
+                                                      head.ns, _lib.ptr(dh), _lib.ptr(part), _lib.stream_ptr()),
+                   "sgc_bayes_head_any_loss_cs_bwd")
+        grads = [None] * 8
+        if need_w:
+            dwb = torch.empty(64, D + 1, dtype=torch.float32, device=h.device)
+            _lib.check(lib.sgc_bayes_head_any_wreduce(_lib.ptr(part), n_part, D, _lib.ptr(dwb), _lib.stream_ptr()),
+                       "sgc_bayes_head_any_wreduce")
+            _split_head_grads(ctx, head, dwb, D, grads)
+        return (dh, *grads) + (None,) * 9
+
+
 class BayesianHead(nn.Module):
     """Plug-and-play hierarchical head on ``[M, input_dim]`` features - drop-in for reference ``model.py:9-34``, trainable: the
     loss flows back through it (into fc3_1 / fc3_2 / fc3_3 / fc5 and into whatever produced h)."""
@@ -751,12 +815,41 @@ class BayesianHead(nn.Module):
             raise ValueError("h must be [M, %d], got %s" % (self.fc5.in_features, tuple(h.shape)))
         return h.to(torch.float32).contiguous()     # autograd hands the gradient back to h in h's own dtype
 
-    def hierarchical_nll(self, h, target, class_weight=None):
+    def _commonsense_args(self, x, commonsense, subject_cat, object_cat):
+        """The checked (bitmaps, subject_cat, object_cat) of a commonsense call on features x [M, D].  Runs before the device check
+        of ``_features``: a wrong argument is a ValueError wherever the tensors live."""
+        from .commonsense import TripletBitmaps
+        if not isinstance(commonsense, TripletBitmaps):
+            raise ValueError("commonsense must be a commonsense.TripletBitmaps")
+        if commonsense.R != self.ng + self.np_ + self.ns:
+            raise ValueError("the bitmaps hold %d relations, the head %d" % (commonsense.R, self.ng + self.np_ + self.ns))
+        if subject_cat is None or object_cat is None:
+            raise ValueError("commonsense needs subject_cat and object_cat")
+        for name, c in (("subject_cat", subject_cat), ("object_cat", object_cat)):
+            if not torch.is_tensor(c) or c.dtype not in (torch.int64, torch.int32) or c.shape != x.shape[:1] or c.device != x.device:
+                raise ValueError("%s must be an int64 / int32 tensor of shape [M] on h's device" % name)
+        if subject_cat.dtype != object_cat.dtype:           # the kernels read both tables in one width
+            subject_cat, object_cat = subject_cat.long(), object_cat.long()
+        if commonsense.aligned.device != x.device:
+            raise ValueError("the bitmaps must be on h's device")
+        return commonsense, subject_cat.contiguous(), object_cat.contiguous()
+
+    def hierarchical_nll(self, h, target, class_weight=None, commonsense=None, subject_cat=None, object_cat=None,
+                         lambda_commonsense=1.0, lambda_cs_weak=0.1, lambda_cs_strong=10.0):
         """The reference's class-weighted hierarchical loss (``train_utils.py:116-157`` with the criteria of ``train_test.py:105-117``)
         of this head on features ``h [M, input_dim]``, as one autograd node and without a host synchronisation: NLL of the super
         category over the connected rows plus, per super category that has rows, the class-weighted NLL of its block.
         ``target [M]`` int64 / int32 in ``[0, R)``; a negative value (or one past ``R``) means "no relation" and skips the row.
-        ``class_weight [R]`` positive, or None for ones.  With no connected row the loss is exactly 0 and all gradients are zero."""
+        ``class_weight [R]`` positive, or None for ones.  With no connected row the loss is exactly 0 and all gradients are zero.
+
+        ``commonsense`` (a ``commonsense.TripletBitmaps`` on h's device, with ``subject_cat`` / ``object_cat [M]`` int64 / int32
+        on the device) adds run_mode ``train_cs`` (``train_utils.py:36-60``) in the same kernels: the result is
+        nll + ``lambda_commonsense`` * penalty, where the penalty is ``lambda_cs_weak`` * the mean largest softmax value of the
+        candidates (row, block arg-max) whose triplet is not aligned + ``lambda_cs_strong`` * that mean over the violated ones, over
+        all rows of this call (defaults: the reference's ``config.yaml:67-69``).  ``last_loss_terms`` = (nll, penalty) and
+        ``last_cs_counts`` = int64 [2] (weak, strong candidates) stay on the device."""
+        if commonsense is not None:
+            commonsense, subject_cat, object_cat = self._commonsense_args(h, commonsense, subject_cat, object_cat)
         x = self._features(h, "hierarchical_nll")
         R = self.ng + self.np_ + self.ns
         if not torch.is_tensor(target) or target.dtype not in (torch.int64, torch.int32) or target.shape != (x.shape[0],):
@@ -766,15 +859,36 @@ class BayesianHead(nn.Module):
             class_weight = torch.as_tensor(class_weight).detach().to(x.device, torch.float32).contiguous()
             if class_weight.shape != (R,):
                 raise ValueError("class_weight must be [%d], got %s" % (R, tuple(class_weight.shape)))
+        if commonsense is not None:
+            with torch.cuda.device(x.device):
+                return _BayesHeadCommonsenseFunction.apply(x, *self._params(), self, target, class_weight, subject_cat, object_cat,
+                                                           commonsense,
+                                                           float(lambda_commonsense), float(lambda_cs_weak), float(lambda_cs_strong))
         with torch.cuda.device(x.device):
             return _BayesHeadLossFunction.apply(x, *self._params(), self, target, class_weight)
 
+    def commonsense_penalty(self, h, subject_cat, object_cat, commonsense, lambda_cs_weak=0.1, lambda_cs_strong=10.0):
+        """The commonsense penalty of ``hierarchical_nll(..., commonsense=)`` alone (``train_utils.py:36-60``; the reference's
+        ``loss_commonsense`` of one classifier call), one autograd node on the same kernels.  Sets ``last_loss_terms`` (its first
+        entry is 0) and ``last_cs_counts``."""
+        cs, sc, oc = self._commonsense_args(h, commonsense, subject_cat, object_cat)
+        x = self._features(h, "commonsense_penalty")
+        with torch.cuda.device(x.device):
+            return _BayesHeadCommonsenseFunction.apply(x, *self._params(), self, None, None, sc, oc, cs, 1.0, float(lambda_cs_weak),
+                                                       float(lambda_cs_strong))
+
     @torch.no_grad()
-    def candidates(self, h):
+    def candidates(self, h, commonsense=None, subject_cat=None, object_cat=None):
         """``(cand_conf [M,3] f32, cand_pred [M,3] int32, sup [M,3] f32)``: per row and super category the maximum log-prob of the
         block and its first arg-max plus the block offset (``evaluator.py:160-174``) - the layout ``Evaluator.accumulate_candidates``
         takes; ``Evaluator_Top3.accumulate_candidates`` takes ``cand_conf.max(1)`` and ``cand_pred`` (``evaluator.py:646-648``).
-        ``cand_conf`` is bit for bit the block maxima of ``forward()``'s outputs.  No autograd."""
+        ``cand_conf`` is bit for bit the block maxima of ``forward()``'s outputs.  No autograd.
+
+        ``commonsense`` (with ``subject_cat`` / ``object_cat``, as in ``hierarchical_nll``) applies the filter of run_mode ``eval_cs``
+        in the same kernel (``evaluator.py:189-194``): ``cand_conf`` is ``-inf`` where the triplet (subject_cat, cand_pred,
+        object_cat) is violated or not aligned; ``cand_pred`` and ``sup`` are unchanged."""
+        if commonsense is not None:
+            commonsense, subject_cat, object_cat = self._commonsense_args(h, commonsense, subject_cat, object_cat)
         x = self._features(h, "candidates")
         M, D = x.shape
         W, b = self._packed(x.device)
@@ -782,6 +896,14 @@ class BayesianHead(nn.Module):
         pred = torch.empty(M, 3, dtype=torch.int32, device=x.device)
         sup = torch.empty(M, 3, dtype=torch.float32, device=x.device)
         f = ctypes.c_float
+        if commonsense is not None:
+            with torch.cuda.device(x.device):
+                _lib.check(_lib.load().sgc_bayes_head_any_candidates_cs(
+                    _lib.ptr(x), _lib.ptr(W), _lib.ptr(b), _lib.ptr(subject_cat), _lib.ptr(object_cat),
+                    int(subject_cat.dtype == torch.int64), _lib.ptr(commonsense.aligned), _lib.ptr(commonsense.violated), commonsense.C,
+                    M, D, self.ng, self.np_, self.ns, f(self.T1), f(self.T2), f(self.T3), _lib.ptr(conf), _lib.ptr(pred), _lib.ptr(sup),
+                    _lib.stream_ptr()), "sgc_bayes_head_any_candidates_cs")
+            return conf, pred, sup
         with torch.cuda.device(x.device):
             _lib.check(_lib.load().sgc_bayes_head_any_candidates(_lib.ptr(x), _lib.ptr(W), _lib.ptr(b), M, D, self.ng, self.np_, self.ns,
                                                                  f(self.T1), f(self.T2), f(self.T3), _lib.ptr(conf), _lib.ptr(pred),
