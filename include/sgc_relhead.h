@@ -481,6 +481,35 @@ int sgc_recall_accumulate_targets(const int* out_pred, const int* out_sub, const
                                   long* targets_pc, long* zs_hits, long* zs_hits_pc, long* zs_targets, long* zs_targets_pc,
                                   void* stream);
 
+/* SGDET / SGCLS TRAINING targets (csrc/kernels_assign.hip): the rows of the same target table - sorted by image, t_ptr [n_img+1]
+ * gives image b its rows - assigned to the ordered pairs of the DETECTED objects' scene (sub_idx / obj_idx / image [n_pairs], pid
+ * [n_obj][pid_ld] and img_ptr [n_img+1] as sgc_scene_tables writes them; cats int64 [n_obj]; boxes f32 [n_obj][4] raw (x0,x1,y0,y1),
+ * 16-byte aligned).  The match test is evaluation's without the predicate (evaluator.py:306-356 with predcls=False); the directed
+ * target is train_utils.py:169-187's, one predicate or -1 per ordered pair.
+ *   Candidate set of a pair p (subject detection s, object detection o, image b): M(p) = the rows t of image b with
+ *   0 <= t_rel < R; label_ok(t_scat, cats[s]) and label_ok(t_ocat, cats[o]), where label_ok(t, c) is t == c, and with equiv (u8
+ *   [n_equiv][n_equiv], NULL = equality only) also true when both classes lie in [0, n_equiv) and equiv[t][c] holds - the row is the
+ *   TARGET's class, the column the detection's, as sgc_recall_accumulate_targets reads the table; and both grid IoUs (int()
+ *   truncation, Python slice clipping, union 0 -> IoU 0) of (boxes[s], t_sbox) and (boxes[o], t_obox) >= iou_thresh.
+ *   matched[p]    = -1 if M(p) is empty, else the row t* of M(p) that maximises q(t) = (I_s*I_o) / (U_s*U_o), the product of the two
+ *                   grid IoUs, compared in exact integer cell counts by 64-bit cross-multiplication (never two floats); on a tie
+ *                   the smallest t.  Cell counts are at most F^2, so the cross products fit in int64 for feature_size <= 128;
+ *                   above that SGC_ERR_ARG.
+ *   directed[p]   = t_rel[matched[p]], or -1.
+ *   raw[p]        = directed[p] if >= 0, else directed of the reversed pair pid[o][s - img_ptr[b]] (what sgc_scene_tables' raw is in
+ *                   PredCLS: the predicate of the unordered pair).
+ *   target_hit[t] = 1 if t is in M(p) for some pair p - also when p ended up with another row - else 0; zeroed HERE on the stream.
+ * So several detections of one ground-truth object all receive its relations, a pair never receives a relation that evaluation
+ * would not credit, and with detections equal to the ground-truth objects the result is the PredCLS target.
+ * One thread per pair, a second tiny launch for raw.  Owns no memory, never synchronises.  n_pairs == 0: returns 0 without a launch
+ * (target_hit is still cleared); n_targets == 0: directed / raw / matched are filled with -1.  SGC_ERR_ARG: a negative count,
+ * R < 1, feature_size outside 1..128, iou_thresh < 0, or a NULL pointer to a table that has entries.  All outputs int32. */
+int sgc_assign_pair_targets(const int* sub_idx, const int* obj_idx, const int* image, int n_pairs, const int* pid, int pid_ld,
+                            const int* img_ptr, const long* cats, const float* boxes, int n_obj, const int* t_ptr, int n_img,
+                            const long* t_rel, const long* t_scat, const long* t_ocat, const float* t_sbox, const float* t_obox,
+                            int n_targets, const unsigned char* equiv, int n_equiv, int R, int feature_size, double iou_thresh,
+                            int* directed, int* raw, int* matched, int* target_hit, void* stream);
+
 /* OpenImages precision counters on the device (evaluator.py:522-557): one wavefront per (image, rank j < min(n_rank, out_count)) of
  * the same ranked lists; image_ptr [n_img+1] / pair_list: the pair rows of every image (pair_list NULL = the rows image_ptr[b] ..
  * image_ptr[b+1]-1).  Over the image's targets (directed != -1, included != 0) with the candidate's labels and predicate:

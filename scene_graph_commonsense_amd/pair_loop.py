@@ -657,6 +657,142 @@ def train_minibatch(model, batch, optimizer=None, reducer=None, scene: Optional[
     return loss
 
 
+class SgdetAssignment:
+    """What ``assign_sgdet_targets`` wrote, all int32 on the device: ``directed`` [P] (the pair's predicate or -1), ``raw`` [P]
+    (``directed``, or the reversed pair's where the pair itself is not connected), ``matched`` [P] (row of the target table or -1),
+    ``target_hit`` [T] (1: the row was a candidate of some pair)."""
+
+    def __init__(self, directed, raw, matched, target_hit):
+        self.directed, self.raw, self.matched, self.target_hit = directed, raw, matched, target_hit
+
+    def counts(self) -> torch.Tensor:
+        """[3] int64 on the device: (targets, targets hit, pairs assigned).  Torch reductions; nothing is read back."""
+        dev = self.matched.device
+        return torch.stack((torch.full((), int(self.target_hit.numel()), dtype=torch.int64, device=dev),
+                            self.target_hit.sum(dtype=torch.int64), (self.matched >= 0).sum(dtype=torch.int64)))
+
+
+_EQUIV_DEVICE = {}
+
+
+def _equiv_table(dev) -> torch.Tensor:
+    """[160,160] u8 device copy of ``evaluator._equiv_matrix()``, uploaded once per device (as ``RecallMeter._equiv`` is)."""
+    key = torch.device(dev)
+    if key not in _EQUIV_DEVICE:
+        from .evaluator import _equiv_matrix
+        _EQUIV_DEVICE[key] = torch.from_numpy(_equiv_matrix().astype(np.uint8)).to(key)
+    return _EQUIV_DEVICE[key]
+
+
+def upload_sgdet_targets(table, n_img: int, dev):
+    """``pairs.sg_target_table``'s numpy arrays plus their per-image row pointer as the device tensors ``assign_sgdet_targets`` takes:
+    (image, relation, subject class, object class, subject box, object box, t_ptr [n_img+1] int32)."""
+    from .pairs import _PinnedRing, _RINGS, sg_target_ptr
+    dev = torch.device(dev)
+    if dev.type != "cuda":
+        raise RuntimeError("upload_sgdet_targets stages the table for sgc_assign_pair_targets: it needs a GPU device (no CPU fallback)")
+    ptr = sg_target_ptr(table[0], n_img)                # host: also checks that the rows are sorted by image
+    # like flatten_scene: one pinned staging buffer, ONE asynchronous copy (seven pageable copies would each wait for the device to
+    # finish the previous step's work); every array starts on a 16-byte boundary
+    kinds = ((np.int32, torch.int32), (np.int64, torch.int64), (np.int64, torch.int64), (np.int64, torch.int64), (np.float32, torch.float32),
+             (np.float32, torch.float32), (np.int32, torch.int32))
+    parts = [np.ascontiguousarray(a, dtype=k[0]) for a, k in zip(tuple(table[:6]) + (ptr,), kinds)]
+    offs, total = [], 0
+    for a in parts:
+        offs.append(total)
+        total += (a.nbytes + 15) // 16 * 16
+    ring = _RINGS.setdefault(dev, _PinnedRing())
+    with torch.cuda.device(dev):
+        slot, host = ring.take(total)
+        hv = host.numpy()
+        for o, a in zip(offs, parts):
+            hv[o:o + a.nbytes] = a.reshape(-1).view(np.uint8)
+        stage = torch.empty(max(total, 16), dtype=torch.uint8, device=dev)
+        stage[:total].copy_(host[:total], non_blocking=True)
+        ring.sent(slot)
+    out = [stage[o:o + a.nbytes].view(k[1]) if a.nbytes else torch.empty(0, dtype=k[1], device=dev) for o, a, k in zip(offs, parts, kinds)]
+    out[4], out[5] = out[4].view(-1, 4), out[5].view(-1, 4)
+    return tuple(out)
+
+
+def assign_sgdet_targets(scene: DeviceScene, table, *, equiv=True, iou_thresh: float = 0.5, num_relations: int,
+                         feature_size: Optional[int] = None) -> SgdetAssignment:
+    """Per-pair training targets of a scene of DETECTED objects from the ground truth as one table (``sgc_assign_pair_targets``;
+    INTEGRATION.md section J has the semantics in full).  ``table``: the device tensors of ``upload_sgdet_targets`` - or the six of
+    ``metrics.upload_sg_targets``, sorted by image; the row pointer is then derived on the device.  A row is a candidate of a pair
+    when evaluation would credit the pair for it apart from the predicate: 0 <= relation < ``num_relations``, labels equal or -
+    ``equiv=True``: the reference's equivalence classes, ``evaluator._equiv_matrix()``; a [n,n] u8 device tensor: that table;
+    ``False`` / ``None``: equality only (OpenImages) - equivalent as ``equiv[target class][detection class]``, both grid IoUs >=
+    ``iou_thresh``.  The pair gets the candidate with the largest product of the two grid IoUs (exact integers; smallest row on a
+    tie).  Sets ``scene.directed`` and ``scene.raw_target``, so that the loss coefficients, the coupled terms and the connectivity
+    statistics see an assigned scene like a PredCLS one.  Nothing synchronises with the host; there is no CPU path."""
+    from .metrics import scene_boxes
+    dev = scene.cats.device
+    if dev.type != "cuda":
+        raise RuntimeError("assign_sgdet_targets runs on the GPU (sgc_assign_pair_targets, no CPU fallback): the scene must be on a cuda device")
+    if len(table) not in (6, 7):
+        raise ValueError("table is (image, relation, subject class, object class, subject box, object box[, t_ptr])")
+    for t in table:
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("assign_sgdet_targets runs on the GPU (no CPU fallback): the target table must be cuda tensors")
+    T = int(table[0].numel())
+    if any(int(t.numel()) != n * T for t, n in zip(table, (1, 1, 1, 1, 4, 4))):
+        raise ValueError("the arrays of the target table disagree in length: [T] image, relation and classes, [T,4] boxes")
+    B, P, n_obj = int(scene.image_feature.shape[0]), int(scene.n_pairs), int(scene.cats.numel())
+    t_image = table[0].to(torch.int32).contiguous()
+    t_rel, t_scat, t_ocat = (t.to(torch.int64).contiguous() for t in table[1:4])
+    t_sbox, t_obox = (t.to(torch.float32).contiguous() for t in table[4:6])
+    if len(table) == 7:
+        t_ptr = table[6].to(torch.int32).contiguous()
+        if int(t_ptr.numel()) != B + 1:
+            raise ValueError("t_ptr must hold one entry per image of the scene plus one")
+    else:
+        t_ptr = torch.searchsorted(t_image, torch.arange(B + 1, dtype=torch.int32, device=dev)).to(torch.int32)
+    eq = None
+    if equiv is True:
+        eq = _equiv_table(dev)
+    elif torch.is_tensor(equiv):
+        if not equiv.is_cuda or equiv.dim() != 2 or equiv.shape[0] != equiv.shape[1]:
+            raise ValueError("equiv must be a square [n,n] cuda tensor")
+        eq = equiv.to(torch.uint8).contiguous()
+    elif equiv not in (False, None):
+        raise ValueError("equiv is True (the reference's classes), False / None (equality only) or a [n,n] u8 cuda tensor")
+    F = int(scene.image_feature.shape[-1]) if feature_size is None else int(feature_size)
+    out = torch.empty(3 * P + T, dtype=torch.int32, device=dev)
+    directed, raw, matched, hit = out[:P], out[P:2 * P], out[2 * P:3 * P], out[3 * P:]
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().sgc_assign_pair_targets(
+            _lib.ptr(scene.sub_idx), _lib.ptr(scene.obj_idx), _lib.ptr(scene.image), P, _lib.ptr(scene.pid), int(scene.pid.shape[1]),
+            _lib.ptr(scene.img_ptr), _lib.ptr(scene.cats), _lib.ptr(scene_boxes(scene, dev)), n_obj, _lib.ptr(t_ptr), B, _lib.ptr(t_rel),
+            _lib.ptr(t_scat), _lib.ptr(t_ocat), _lib.ptr(t_sbox), _lib.ptr(t_obox), T, _lib.ptr(eq), 0 if eq is None else int(eq.shape[0]),
+            int(num_relations), F, ctypes.c_double(float(iou_thresh)), _lib.ptr(directed), _lib.ptr(raw), _lib.ptr(matched), _lib.ptr(hit),
+            _lib.stream_ptr()), "sgc_assign_pair_targets")
+    scene.directed, scene.raw_target = directed, raw
+    return SgdetAssignment(directed, raw, matched, hit)
+
+
+def train_sgdet_minibatch(model, image_feature, image_depth, categories_pred, bbox_pred, targets, optimizer=None, reducer=None,
+                          sub2super=None, equiv=True, iou_thresh: float = 0.5, workspace_budget: Optional[float] = None,
+                          streams: Optional[int] = None, input_grads: bool = False, **loss_kw):
+    """One optimisation step on the DETECTED objects of an SGDET minibatch (``BASELINE.json`` configs[3]): ``train_minibatch`` over every
+    ordered pair of the predicted objects (per-image lists ``categories_pred`` / ``bbox_pred`` as ``evaluate_sgdet_minibatch`` takes
+    them), with the ground truth ``targets`` = (relationships, subj_or_obj, categories_target, bbox_target) assigned to those pairs on
+    the device (``assign_sgdet_targets``): a pair is trained towards a relation exactly when evaluation would credit it for that
+    relation.  SGCLS training is the same call with the lists ``match_object_categories`` returns (ground-truth boxes, predicted
+    labels).  Every relation is collected (``sg_target_table(drop_last_graph_object=False)``).  The table is built and uploaded
+    before anything is enqueued behind it; nothing synchronises between the assignment and the step.  ``equiv`` / ``iou_thresh`` as
+    ``assign_sgdet_targets``; everything else - ``image_feature_aug=`` and ``commonsense=`` included - as ``train_minibatch``.
+    Returns the loss; ``model.last_assignment`` holds the ``SgdetAssignment``."""
+    from .pairs import sg_target_table
+    table = upload_sgdet_targets(sg_target_table(*targets, drop_last_graph_object=False), len(categories_pred),
+                                 next(model.parameters()).device)
+    cfg, dev, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
+    model.last_assignment = assign_sgdet_targets(scene, table, equiv=equiv, iou_thresh=iou_thresh, num_relations=cfg.num_relations,
+                                                 feature_size=cfg.feature_size)
+    return train_minibatch(model, batch, optimizer, reducer, scene=scene, workspace_budget=workspace_budget, streams=streams,
+                           input_grads=input_grads, **loss_kw)
+
+
 def _drive_input_autograd(batch, aug, grads):
     """Hand the head's input gradients to the autograd graph that produced the minibatch's tensors (those that require grad)."""
     roots, gs = [], []
@@ -749,6 +885,9 @@ def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, 
             raise ValueError("the contrastive / commonsense terms need relation targets in the scene")
     coefs = model.minibatch_loss_coefficients(scene, kw.pop("class_weight", None), kw.pop("lambda_connectivity", 0.1),
                                               kw.pop("lambda_not_connected", 1.0))
+    # a scene whose targets were ASSIGNED (assign_sgdet_targets: the batch of detected objects has no relationship lists): every group
+    # gets its rows of them - the group's pair order is the minibatch's restricted to its images - instead of list slices
+    assigned = getattr(batch, "relationships", None) is None and scene.directed is not None
     subs = []
     for a, b in groups:
         rows = _group_rows(scene, a, b)
@@ -758,6 +897,9 @@ def _train_image_groups(model, cfg, batch, scene: DeviceScene, groups, reducer, 
         sub_b = slice_batch(batch, a, b)
         sub = flatten_scene(cfg, sub_b, dev)
         assert sub.n_pairs == int(rows.numel())
+        if assigned:
+            sub.directed = scene.directed[rows].contiguous()
+            sub.raw_target = None if scene.raw_target is None else scene.raw_target[rows].contiguous()
         sub._batch = sub_b
         subs.append((rows, sub))
     coupled, loss_c = (None, None)

@@ -443,16 +443,21 @@ def _triangle(rows, G: int) -> np.ndarray:
     return np.concatenate([_host_array(r).reshape(-1)[:g] for g, r in enumerate(rows, start=1)])
 
 
-def sg_target_table(relationships, subj_or_obj, categories_target, bbox_target):
+def sg_target_table(relationships, subj_or_obj, categories_target, bbox_target, drop_last_graph_object: bool = True):
     """The ground-truth triples of a minibatch as ONE table for ``sgc_recall_accumulate_targets`` (``metrics.RecallMeter.update(
     sg_targets=...)``): numpy arrays (image int32 [T], relation int64 [T], subject class int64 [T], object class int64 [T], subject box
     f32 [T,4], object box f32 [T,4]).  The rows are ``match_target_sgd``'s per-image lists concatenated in image order - images
     without relations contribute none - with its loop bound (``utils.py:294-350``: relations whose graph object is the last object of
-    an image are not collected).  One pass of array operations per image, no per-element appends."""
+    an image are not collected).  One pass of array operations per image, no per-element appends.
+    ``drop_last_graph_object=False`` collects EVERY relation, those of the last object included: the loop bound is an artefact of
+    evaluation, and training on detected objects (``pair_loop.train_sgdet_minibatch``) must not drop supervised relations silently.
+    The rows are sorted by image either way; ``sg_target_ptr`` gives every image its row range."""
     host = _host_array
     parts = ([], [], [], [], [], [])
     for b in range(len(relationships)):
         G = len(relationships[b])                    # graph objects 1 .. G-1 (the reference's bound; the image has G+1 objects)
+        if not drop_last_graph_object:
+            G += 1                                   # ... 1 .. G: the last object too
         if G < 2:
             continue
         flag, rel = _triangle(subj_or_obj[b], G), _triangle(relationships[b], G).astype(np.int64)
@@ -471,3 +476,11 @@ def sg_target_table(relationships, subj_or_obj, categories_target, bbox_target):
     empty = (np.zeros(0, np.int32), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, 4), np.float32),
              np.zeros((0, 4), np.float32))
     return tuple(np.concatenate(p) if p else e for p, e in zip(parts, empty))
+
+
+def sg_target_ptr(image_column, n_img: int) -> np.ndarray:
+    """[n_img+1] int32: rows ``ptr[b] .. ptr[b+1]-1`` of a target table (``sg_target_table``, sorted by image) belong to image b."""
+    col = np.asarray(image_column, dtype=np.int64).reshape(-1)
+    if col.size > 1 and bool((np.diff(col) < 0).any()):
+        raise ValueError("the target table must be sorted by image")
+    return np.searchsorted(col, np.arange(int(n_img) + 1), side="left").astype(np.int32)
