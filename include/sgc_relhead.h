@@ -799,6 +799,7 @@ int sgc_dbg_conv_nt(int elem, const void* A, const void* B, void* C, int n_img, 
 int sgc_dbg_gemm_tn(int elem, const void* A, const void* B, float* C, int M, int N, int K, long lda, long ldb, int splits, int* slabs, void* stream);
 int sgc_dbg_conv_tn(int elem, const void* A, const void* B, float* C, int M, int n_img, int lgS, int Cin, int splits, int* slabs, void* stream);
 int sgc_dbg_tr_probe(const int* addr, short* out, void* stream);
+int sgc_dbg_mfma16_probe(int elem, const void* a, const void* b, float* c, void* stream);
 int sgc_dbg_mfma_rate(float* out, int blocks, int iters, int mode, void* stream);
 int sgc_dbg_smfmac_probe(const void* a, const void* b, const int* idx, float* c, int abid, void* stream);
 

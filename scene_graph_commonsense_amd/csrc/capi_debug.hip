@@ -69,6 +69,21 @@ int sgc_dbg_tr_probe(const int* addr, short* out, void* stream) {
     return SGC_OK;
 }
 
+// v_mfma_f32_16x16x32_{f16,bf16} layout probe (mfma16 of gemm_nt.h): lane l passes a[l*8 .. +7] and b[l*8 .. +7]; c[l*4 + r] = register r
+__global__ void mfma16_probe_kernel(const u16* a, const u16* b, float* c, int elem) {
+    const int l = threadIdx.x;
+    s16x8 av, bv;
+    for (int i = 0; i < 8; ++i) { av[i] = (short)a[l * 8 + i]; bv[i] = (short)b[l * 8 + i]; }
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    acc = elem == ELEM_F16 ? mfma16<ELEM_F16>(av, bv, acc) : mfma16<ELEM_BF16>(av, bv, acc);
+    for (int r = 0; r < 4; ++r) c[l * 4 + r] = acc[r];
+}
+int sgc_dbg_mfma16_probe(int elem, const void* a, const void* b, float* c, void* stream) {
+    SGC_LAUNCH(mfma16_probe_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const u16*)a, (const u16*)b, c, elem);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
 // v_smfmac_f32_32x32x32_bf16 semantics probe: every lane supplies its 8 compressed A values, 16 B values and the index word
 __global__ void smfmac_probe_kernel(const u16* a, const u16* b, const int* idx, float* c, int abid) {
     typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));

@@ -1,16 +1,29 @@
 // NT GEMM for gfx950:  C[M,N] = A[M,K] * B[N,K]^T, 16-bit inputs (f16 or bf16), f32 accumulate on
-// v_mfma_f32_32x32x16_{f16,bf16}.  128x128x64 block tile, 4 wavefronts (2x2), each 64x64 = 2x2 MFMA tiles.
+// v_mfma_f32_16x16x32_{f16,bf16}.  128x128x64 block tile, 4 wavefronts (2x2), each 64x64 = 4x4 MFMA tiles.
+//
+// THE ACCUMULATION CONTRACT.  Several tests demand bit equality between runs that reach DIFFERENT blocks of this family for the
+// same output element (one image group against many, shared against per-pair conv3, conv2 on halves against whole maps): the
+// block is chosen by the size of the problem.  They agree because every NT kernel here (gemm_nt_kernel in both block sizes,
+// gemm_nt_pp_kernel in all its forms, conv16_halo_pp_kernel)
+//   * adds, into each output element, ONE 16x16x32 instruction per 32 consecutive k (lane group l>>4 supplies k = 8*(l>>4) .. +7),
+//   * in increasing k of its own K order (plain: k; convolutions: (64-channel chunk, tap, channel)),
+//   * and never splits or reorders that sequence (no split-K, no second accumulator per element).
+// Which lane or register holds an element, and which operand is passed first, does not enter.  A kernel that joins the family
+// keeps all three; the TN (weight gradient) and sparse kernels are compared only among themselves and run 32x32x16.
+// Why this shape: at equal instruction cycles per FLOP the launches measured shorter on it than on 32x32x16 (conv3 forward over the
+// listed windows -9 %, the step -1.0 ... -1.1 ms); in a counter pass of each build that launch ran +3 % wave cycles at an effective clock of
+// 1.53 against 1.41 GHz (GRBM_GUI_ACTIVE / 8 / duration; profiles/mfma_shape_ab.txt).
 //
 //  * Operands go HBM -> LDS with global_load_lds_dwordx4 (no VGPR round trip), double buffered, one
 //    barrier per K tile.  The LDS image is lane-linear, so the bank swizzle (16-byte chunk index XOR
-//    ((row>>1)&7), conflict-free for the 4x16-lane groups of ds_read_b128 at a 128-byte row pitch) is
+//    ((row>>1)&7), conflict-free for the lane groups of ds_read_b128 - {0-3,12-15,20-27}, {4-11,16-19,28-31}, the same + 32 -
+//    at a 128-byte row pitch: a group holds the 16 rows of a fragment, 12 of them at chunk c and 4 at c^1) is
 //    applied to the per-lane SOURCE address and again on the fragment read.
 //  * AMODE_CONV turns the A operand into an implicit 3x3 convolution over a zero-padded channels-last
 //    image [img][S+2][S+2][Cin]: K index = (c/64, tap, c%64); every A row is a pixel whose address is shifted by
 //    the tap, so no im2col buffer exists.  Rows are enumerated window-major (m = 4*window + q,
 //    q = dy*2+dx inside a 2x2 pooling window) so that a 2x2 max-pool is a pure in-register max over the
-//    four accumulator registers a lane holds for one window (MFMA C layout: row = (reg&3) + 8*(reg>>2)
-//    + 4*(lane>>5)).
+//    four accumulator registers a lane holds for one window (MFMA C layout: column = lane&15, row = 4*(lane>>4) + reg).
 //  * Epilogues fuse what the reference does after each contraction (bias, tanh, ReLU, dropout, 2x2
 //    max-pool + argmax, one-hot label columns of fc2 as a per-object row gather, ReLU-mask for dgrad).
 #pragma once
@@ -64,6 +77,25 @@ __device__ __forceinline__ f32x16 mfma32(s16x8 a, s16x8 b, f32x16 c) {
     }
 }
 
+// The instruction of the NT family.  Lane l supplies row (a) / column (b) l&15 with k = 8*(l>>4) .. +7 of the 32, and holds
+// column l&15, rows 4*(l>>4) + r of the 16x16 result (sgc_dbg_mfma16_probe, tests/test_mfma16_gpu.py).
+template <int ELEM>
+__device__ __forceinline__ f32x4 mfma16(s16x8 a, s16x8 b, f32x4 c) {
+    if constexpr (ELEM == ELEM_F16) {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+    } else {
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+    }
+}
+
+// Row, inside a wave's output tile, of row r (0..15) of the wave's 16-row fragment i.  HALO (conv16_halo_pp_kernel): the two
+// fragments of a 32-row band (the 8 windows of one window row of the map) take its even and its odd windows.
+template <bool HALO>
+__device__ __forceinline__ int frag_row(int i, int r) {
+    if constexpr (HALO) return (i >> 1) * 32 + ((2 * (r >> 2) + (i & 1)) << 2) + (r & 3);
+    else return i * 16 + r;
+}
+
 // window-major row -> element offset of padded pixel (tap 0,0) in [img][S+2][S+2][Cin]
 __device__ __forceinline__ long conv_row_base(int m, int lgS, int Cin) {
     const int S = 1 << lgS;
@@ -75,50 +107,48 @@ __device__ __forceinline__ long conv_row_base(int m, int lgS, int Cin) {
     return ((long)(img * (S + 2) + y) * (S + 2) + x) * Cin;
 }
 
-template <int ELEM, int EPI, int TM, int TN, bool GATHER = false>
-__device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x16 (&acc)[TM][TN], int m0, int n0, int wr, int wc, int lane, int m_limit = -1) {
+// FM x FN fragments of 16 x 16 per wave: fragment (i, j) holds rows frag_row(i, 4*(lane>>4) + r), column j*16 + (lane&15) of the wave's tile
+template <int ELEM, int EPI, int FM, int FN, bool GATHER = false, bool HALO = false>
+__device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x4 (&acc)[FM][FN], int m0, int n0, int wr, int wc, int lane, int m_limit = -1) {
     const int M = GATHER ? m_limit : p.M;
-    const int h = lane >> 5, cl = lane & 31;
+    const int g = lane >> 4, cl = lane & 15;
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
+    for (int i = 0; i < FM; ++i) {
 #pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int col = n0 + wc * TN * 32 + j * 32 + cl;
-            const int rbase = m0 + wr * TM * 32 + i * 32;
+        for (int j = 0; j < FN; ++j) {
+            const int col = n0 + wc * FN * 16 + j * 16 + cl;
+            const int rbase = m0 + wr * FM * 16 + frag_row<HALO>(i, 4 * g);       // the lane's four rows: one pooling window
             const float bias = p.bias ? p.bias[col] : 0.f;
             if constexpr (EPI == EPI_POOL) {
                 u16* out = reinterpret_cast<u16*>(p.C);
+                float v = acc[i][j][0];
+                int am = 0;
 #pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    float v = acc[i][j][4 * w];
-                    int am = 0;
+                for (int q = 1; q < 4; ++q) {
+                    const float t = acc[i][j][q];
+                    if (t > v) { v = t; am = q; }
+                }
+                v += bias;
+                const int prow = rbase >> 2;
+                if (prow * 4 < M) {
+                    long arow = prow, yrow = prow;
+                    if constexpr (GATHER) {
+                        arow = p.gather[prow]; yrow = p.dest ? p.dest[prow] : arow;
+                        if (p.raw && prow >= p.raw_first) {
 #pragma unroll
-                    for (int q = 1; q < 4; ++q) {
-                        const float t = acc[i][j][4 * w + q];
-                        if (t > v) { v = t; am = q; }
-                    }
-                    v += bias;
-                    const int prow = (rbase >> 2) + 2 * w + h;
-                    if (prow * 4 < M) {
-                        long arow = prow, yrow = prow;
-                        if constexpr (GATHER) {
-                            arow = p.gather[prow]; yrow = p.dest ? p.dest[prow] : arow;
-                            if (p.raw && prow >= p.raw_first) {
-#pragma unroll
-                                for (int q = 0; q < 4; ++q) p.raw[((long)(prow - p.raw_first) * 4 + q) * p.ldc + col] = acc[i][j][4 * w + q];
-                            }
+                            for (int q = 0; q < 4; ++q) p.raw[((long)(prow - p.raw_first) * 4 + q) * p.ldc + col] = acc[i][j][q];
                         }
-                        else if (p.wm_goff) yrow = p.wm_goff[prow & 63] + (prow >> 6);
-                        if (!(v > 0.f)) { v = 0.f; am = 4; }        // ReLU killed: no gradient path
-                        out[yrow * p.ldc + col] = to_elem<ELEM>(v);
-                        if (p.C2) p.C2[yrow * p.ldc + col] = f32_to_bf16_bits(v);
-                        if (p.argmax) p.argmax[arow * p.ldc + col] = (unsigned char)am;
                     }
+                    else if (p.wm_goff) yrow = p.wm_goff[prow & 63] + (prow >> 6);
+                    if (!(v > 0.f)) { v = 0.f; am = 4; }        // ReLU killed: no gradient path
+                    out[yrow * p.ldc + col] = to_elem<ELEM>(v);
+                    if (p.C2) p.C2[yrow * p.ldc + col] = f32_to_bf16_bits(v);
+                    if (p.argmax) p.argmax[arow * p.ldc + col] = (unsigned char)am;
                 }
             } else {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    const int row = rbase + (r & 3) + 8 * (r >> 2) + 4 * h;
+                for (int r = 0; r < 4; ++r) {
+                    const int row = rbase + r;
                     if (row >= M) continue;
                     float v = acc[i][j][r];
                     long o = (long)row * p.ldc + col;
@@ -150,39 +180,36 @@ __device__ __forceinline__ void nt_epilogue(const NtParams& p, f32x16 (&acc)[TM]
 }
 
 // f32 output of the 8-wave 256x256 block with the operands SWAPPED in the MFMA (acc = B_frag x A_frag^T): a lane then owns one output
-// ROW (m = lane & 31) and four consecutive COLUMNS per register quad, so the tile leaves as 32 16-byte stores per lane instead of the
-// 128 4-byte stores of the plain C layout (fc1 over window-major rows: 5 GB of f32 products per launch, K = 1024 - the epilogue is
-// as long as the main loop).  Same products, same order of accumulation over k: bit-identical to EPI_STORE_F32.
-__device__ __forceinline__ void nt_epilogue_f32t(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane) {
-    const int h = lane >> 5, cl = lane & 31;
+// ROW (m = lane & 15) and the four consecutive COLUMNS 4*(lane>>4) .. +3 of every fragment, so the tile leaves as 32 16-byte stores per
+// lane instead of the 128 4-byte stores of the plain C layout (fc1 over window-major rows: 5 GB of f32 products per launch, K = 1024 -
+// the epilogue is as long as the main loop).  Same products, same order of accumulation over k: bit-identical to EPI_STORE_F32.
+__device__ __forceinline__ void nt_epilogue_f32t(const NtParams& p, f32x4 (&acc)[8][4], int m0, int n0, int wr, int wc, int lane) {
+    const int g = lane >> 4, cl = lane & 15;
     float* out = reinterpret_cast<float*>(p.C);
     if (!out) return;                                  // no output buffer: the launch without its stores
     const int g_first = p.Cx ? p.wm_goff[p.tile_group[m0 >> 8]] + p.x_first : 0;      // first X row of this tile's group
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int row = m0 + wr * 128 + i * 32 + cl;
+    for (int i = 0; i < 8; ++i) {
+        const int row = m0 + wr * 128 + i * 16 + cl;
         if (row >= p.M) continue;
         const bool xrow = p.Cx && row >= g_first;
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-#pragma unroll
-            for (int rq = 0; rq < 4; ++rq) {
-                const int col = n0 + wc * 64 + j * 32 + 8 * rq + 4 * h;
-                f32x4 v = {acc[i][j][4 * rq], acc[i][j][4 * rq + 1], acc[i][j][4 * rq + 2], acc[i][j][4 * rq + 3]};
-                if (p.bias) {
-                    const f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + col);
-                    v += b;
-                }
-                if (xrow) {                                // a pair-specific row: one of ~7 products added per pair, f16 carries it
-                    uint2 hv;
-                    hv.x = (unsigned)f32_to_f16_bits(v[0]) | ((unsigned)f32_to_f16_bits(v[1]) << 16);
-                    hv.y = (unsigned)f32_to_f16_bits(v[2]) | ((unsigned)f32_to_f16_bits(v[3]) << 16);
-                    *reinterpret_cast<uint2*>(p.Cx + (long)row * p.N + col) = hv;
-                    continue;
-                }
-                f32x4* dst = reinterpret_cast<f32x4*>(out + (long)row * p.ldc + col);
-                *dst = v;
+        for (int j = 0; j < 4; ++j) {
+            const int col = n0 + wc * 64 + j * 16 + 4 * g;
+            f32x4 v = acc[i][j];
+            if (p.bias) {
+                const f32x4 b = *reinterpret_cast<const f32x4*>(p.bias + col);
+                v += b;
             }
+            if (xrow) {                                // a pair-specific row: one of ~7 products added per pair, f16 carries it
+                uint2 hv;
+                hv.x = (unsigned)f32_to_f16_bits(v[0]) | ((unsigned)f32_to_f16_bits(v[1]) << 16);
+                hv.y = (unsigned)f32_to_f16_bits(v[2]) | ((unsigned)f32_to_f16_bits(v[3]) << 16);
+                *reinterpret_cast<uint2*>(p.Cx + (long)row * p.N + col) = hv;
+                continue;
+            }
+            f32x4* dst = reinterpret_cast<f32x4*>(out + (long)row * p.ldc + col);
+            *dst = v;
         }
     }
 }
@@ -217,7 +244,7 @@ __device__ __forceinline__ void supertile_map_g(int id, int tiles_m, int tiles_n
 }
 
 // LDS-staged epilogue for 16-bit EPI_STORE outputs of the 8-wave 256x256 block (conv3 / fc1 / conv2 data gradients write
-// 4-9 GB per launch): the MFMA C layout gives each lane ONE column of 16 rows per tile, i.e. 2-byte global stores.  Here
+// 4-9 GB per launch): the MFMA C layout gives each lane ONE column (four rows per fragment), i.e. 2-byte global stores.  Here
 // each wave transposes its 128x64 sub-tile through its own 18 KiB LDS region (row pitch 144 B): neighbouring lanes swap a
 // value (DPP) so that every lane writes one packed dword (two adjacent columns), then the wave reads rows back as 16-byte
 // pieces and issues 16 full-line 16-byte stores per lane instead of 128 2-byte ones.  Needs 8 x 16 KiB of LDS.
@@ -231,33 +258,35 @@ constexpr int EPI_LDS_BYTES = 8 * 128 * EPI_LDS_PITCH;
 // MASK (EPI_RELUMASK through this epilogue, round 5): the value is multiplied by p.scale before it is rounded, and the read-back zeroes the
 // elements whose forward activation p.mask_src (f16, the output's shape) is not > 0 - 16-byte mask loads beside the 16-byte stores; the
 // generic epilogue did this with a 2-byte load and a 2-byte store per element (fc2's data gradient: 0.50 ms for 0.5 GB).  Same values.
-template <int ELEM, bool MASK = false>
-__device__ __forceinline__ void nt_epilogue_store16(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane,
+// On the 16x16 fragments a lane holds rows 4*(lane>>4) + r of one column: the (even, odd) lane pair swaps, every lane writes the packed dword of one row.
+// (The sparse data gradient keeps 32-row accumulators and its own copy of this epilogue, csrc/kernels_dgrad_sp.hip.)
+// The rows 4g of the four lane groups are all even: besides the half swap of odd rows, rows with bit 2 set swap their 32-byte quarters, so the
+// 32 lanes of a ds_write_b32 pass (g = 0,1 or 2,3; 8 dwords each for even and odd rows) cover 32 distinct banks; the read-back applies both.
+template <int ELEM, bool MASK = false, bool HALO = false>
+__device__ __forceinline__ void nt_epilogue_store16(const NtParams& p, f32x4 (&acc)[8][4], int m0, int n0, int wr, int wc, int lane,
                                                     int wid, char* smem) {
     __syncthreads();                                   // every wave is done reading operand tiles
     char* reg = smem + wid * (128 * EPI_LDS_PITCH);
-    const int h = lane >> 5, cl = lane & 31;
+    const int g = lane >> 4, cl = lane & 15;
     const bool odd = cl & 1;
+    constexpr int QB = HALO ? 8 : 4;                   // the row bit that lane>>4 & 1 lands on (frag_row)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 8; ++i) {
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wc * 64 + j * 32 + cl;
+        for (int j = 0; j < 4; ++j) {
+            const int col = n0 + wc * 64 + j * 16 + cl;
             const float bias = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
-            for (int rp = 0; rp < 8; ++rp) {
+            for (int rp = 0; rp < 2; ++rp) {
                 float v0 = acc[i][j][2 * rp] + bias, v1 = acc[i][j][2 * rp + 1] + bias;
                 if constexpr (MASK) { v0 *= p.scale; v1 *= p.scale; }
                 const float recv = __shfl_xor(odd ? v0 : v1, 1);
-                const int r0 = ((2 * rp) & 3) + 8 * ((2 * rp) >> 2) + 4 * h;       // row of register 2rp; register 2rp+1 is r0+1
                 const float flo = odd ? recv : v0, fhi = odd ? v1 : recv;
                 unsigned packed;
                 if constexpr (ELEM == ELEM_BF16) packed = f32x2_to_bf16x2_bits(flo, fhi);      // one v_cvt_pk_bf16_f32
                 else packed = (unsigned)to_elem<ELEM>(flo) | ((unsigned)to_elem<ELEM>(fhi) << 16);
-                const int row = i * 32 + r0 + (odd ? 1 : 0);
-                // odd rows keep their two 64-byte halves swapped: the dwords of an (even, odd) lane pair - rows R and R + 1, same column -
-                // then fall on different banks (conflict-free writes), and the read-back below stays conflict-free
-                *reinterpret_cast<unsigned*>(reg + row * EPI_LDS_PITCH + (((j * 32 + (cl & ~1)) * 2) ^ ((row & 1) << 6))) = packed;
+                const int row = frag_row<HALO>(i, 4 * g + 2 * rp) + (odd ? 1 : 0);
+                *reinterpret_cast<unsigned*>(reg + row * EPI_LDS_PITCH + (((j * 16 + (cl & ~1)) * 2) ^ ((row & 1) << 6) ^ ((row & QB) ? 32 : 0))) = packed;
             }
         }
     }
@@ -267,7 +296,7 @@ __device__ __forceinline__ void nt_epilogue_store16(const NtParams& p, f32x16 (&
 #pragma unroll
     for (int it = 0; it < 16; ++it) {
         const int rowl = it * 8 + rsub;
-        uint4 v = *reinterpret_cast<const uint4*>(reg + rowl * EPI_LDS_PITCH + ((c8 * 16) ^ ((rowl & 1) << 6)));
+        uint4 v = *reinterpret_cast<const uint4*>(reg + rowl * EPI_LDS_PITCH + ((c8 * 16) ^ ((rowl & 1) << 6) ^ ((rowl & QB) ? 32 : 0)));
         const int row = m0 + wr * 128 + rowl;
         if (row < p.M) {
             const long o = (long)row * p.ldc + n0 + wc * 64 + c8 * 8;
@@ -284,7 +313,7 @@ __device__ __forceinline__ void nt_epilogue_store16(const NtParams& p, f32x16 (&
     }
 }
 
-// Block configuration: WR x WC wavefronts, each owning a (TM*32) x (TN*32) output tile.
+// Block configuration: WR x WC wavefronts, each owning a (TM*32) x (TN*32) output tile = FM x FN = 2TM x 2TN fragments of 16 x 16.
 //   small: 2x2 waves of 64x64   -> 128x128 block, 64 KiB LDS, 2 blocks/CU  (small problems, N % 256 != 0)
 //   big  : 2x4 waves of 128x64  -> 256x256 block, 128 KiB LDS, 1 block/CU  (half the LDS bytes per MFMA)
 template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN>
@@ -350,25 +379,17 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams
 
     // ---- fragment read addresses
     const int wr = wid / WC, wc = wid % WC;
-    const int kh = lane >> 5;
-    int a_off[TM], a_sw[TM], b_off[TN], b_sw[TN];
+    // fragment i of a wave = 16 rows; the row swizzle (row>>1)&7 only depends on lane&15 (fragments start at multiples of 16 rows)
+    const int kg = lane >> 4, sw = ((lane & 15) >> 1) & 7;
+    constexpr int FM = 2 * TM, FN = 2 * TN;
+    const int a_rd = (wr * TM * 32 + (lane & 15)) * 128, b_rd = (wc * TN * 32 + (lane & 15)) * 128;
+    f32x4 acc[FM][FN];
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
-        const int ra = wr * TM * 32 + i * 32 + (lane & 31);
-        a_off[i] = ra * 128; a_sw[i] = (ra >> 1) & 7;
-    }
+    for (int i = 0; i < FM; ++i)
 #pragma unroll
-    for (int i = 0; i < TN; ++i) {
-        const int rb = wc * TN * 32 + i * 32 + (lane & 31);
-        b_off[i] = rb * 128; b_sw[i] = (rb >> 1) & 7;
-    }
-    f32x16 acc[TM][TN];
+        for (int j = 0; j < FN; ++j)
 #pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
 
     const int nk = p.K >> 6;
     stage(0, 0);
@@ -379,25 +400,25 @@ __global__ __launch_bounds__(WR * WC * 64, 2) void gemm_nt_kernel(const NtParams
         const char* ab = smem + (kt & 1) * BUF_BYTES;
         const char* bb = ab + A_BYTES;
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            const int c = ks * 2 + kh;
-            s16x8 af[TM], bf[TN];
+        for (int ks = 0; ks < 2; ++ks) {               // one instruction step = 32 k = chunks 4*ks .. +3, one per lane group
+            const int ko = ((ks * 4 + kg) ^ sw) << 4;
+            s16x8 af[FM], bf[FN];
 #pragma unroll
-            for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(ab + a_off[i] + ((c ^ a_sw[i]) << 4));
+            for (int i = 0; i < FM; ++i) af[i] = *reinterpret_cast<const s16x8*>(ab + a_rd + i * 2048 + ko);
 #pragma unroll
-            for (int i = 0; i < TN; ++i) bf[i] = *reinterpret_cast<const s16x8*>(bb + b_off[i] + ((c ^ b_sw[i]) << 4));
+            for (int i = 0; i < FN; ++i) bf[i] = *reinterpret_cast<const s16x8*>(bb + b_rd + i * 2048 + ko);
 #pragma unroll
-            for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < FM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) acc[i][j] = mfma32<ELEM>(af[i], bf[j], acc[i][j]);
+                for (int j = 0; j < FN; ++j) acc[i][j] = mfma16<ELEM>(af[i], bf[j], acc[i][j]);
         }
     }
 
     if constexpr (EPI == EPI_STORE && TM == 4 && TN == 2 && WR * WC == 8) {
         if (p.epi_lds) { nt_epilogue_store16<ELEM>(p, acc, m0, n0, wr, wc, lane, wid, smem); return; }
     }
-    if constexpr (AMODE == AMODE_CONV_GATHER) nt_epilogue<ELEM, EPI, TM, TN, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
-    else nt_epilogue<ELEM, EPI, TM, TN>(p, acc, m0, n0, wr, wc, lane);
+    if constexpr (AMODE == AMODE_CONV_GATHER) nt_epilogue<ELEM, EPI, FM, FN, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
+    else nt_epilogue<ELEM, EPI, FM, FN>(p, acc, m0, n0, wr, wc, lane);
 }
 
 template <int ELEM, int AMODE, int EPI, int WR, int WC, int TM, int TN>

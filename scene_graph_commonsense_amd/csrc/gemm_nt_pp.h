@@ -5,8 +5,9 @@
 //    issues its LDS fragment reads and its share of the global->LDS prefetch, the other issues MFMAs, and they swap at
 //    every s_barrier.  The 2-stage loop of gemm_nt_kernel leaves both waves of a SIMD reading LDS at the same time after
 //    each barrier (LDS-read + MFMA alone: 1450 TFLOP/s-equivalent there, 1555 here).
-//  * A K tile is consumed in two phases = the two 64x64 halves of the wave's 128x64 output, 16 MFMAs per barrier slot:
-//    phase X (rows a0) reads the A0 half and both B halves (16 ds_read_b128), phase Y (rows a1) reads A1 (8).
+//  * A K tile is consumed in two phases = the two 64x64 halves of the wave's 128x64 output, 32 MFMAs (v_mfma_f32_16x16x32: 4 x 4
+//    fragments x 2 steps of 32 k) per barrier slot: phase X (rows a0) reads the A0 half and both B halves (16 ds_read_b128), phase Y
+//    (rows a1) reads A1 (8).  The accumulation order is the family's contract (top of gemm_nt.h).
 //  * Operands are staged in HALF tiles (128 rows x 64 k = 16 KiB = 2 global_load_lds per wave): A0/A1 = rows
 //    {0-63,128-191}/{64-127,192-255} of the block (the a-half of both wave rows), B0/B1 = the b-half of the four wave
 //    columns.  Eight 16 KiB slots (two K tiles) form a ring; a half tile's successor (two K tiles ahead) is issued in
@@ -19,12 +20,15 @@
 //        overwrite is issued in phase p+1 (slot >= 2p+2).
 //  Measured on 32768x4096x8192 bf16, random operands, one box: 2-stage loop 1.91 ms (1150 TFLOP/s), this schedule
 //  1.77 ms (1243), with the XCD-aware tile walk 1.74 ms (1264).  Variants measured and dropped: four phases per K tile
-//  (8 MFMAs per slot, vmcnt(12)) 2.0 ms - the ~85-cycle barrier slot overhead is paid twice as often; s_setprio(1)
+//  (half the MFMAs per slot, vmcnt(12)) 2.0 ms - the ~85-cycle barrier slot overhead is paid twice as often; s_setprio(1)
 //  around the MFMA section -1 %; issuing the last 1/2/4 MFMAs of a slot AFTER its closing barrier (to keep the pipe fed
 //  across the barrier) -7/-9/-11 %.  Row strides: padding the 128 KiB rows of the fc1 operands (K = 65536) by 128 B ... 1152 B
 //  moved the launch by <= 1 % (13.71 -> 13.55 ms): the power-of-two stride is not what costs the L2 its hits.  Counters for
 //  that launch: 56 GB of L2 misses against 25 GB for perfectly shared 4x8 patches (blocks of a patch drift apart in K) and an
 //  effective clock of 1.40 GHz (conv3 data gradient: 1.90) - the chip's power budget, not the schedule, sets these rates.
+//  The figures above were taken on the 32-row instruction (K = 16) this block ran until the A/B of profiles/mfma_shape_ab.txt: the same
+//  schedule on 16x16x32 (equal cycles per FLOP, 24 ds_read_b128 per wave and K tile as before) runs conv3 forward over the listed windows
+//  in 6.28 ms against 6.91 ms (three alternated runs each, no overlap), the step 0.9 - 1.1 ms faster; effective clock of that launch under the profiler 1.53 against 1.41 GHz (same file).
 #pragma once
 
 #define SGC_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
@@ -88,8 +92,8 @@ __device__ __forceinline__ bool xcd_patch_map_aligned(int id, int tiles_m, int t
 // W_t, i.e. a product with K = 1024 x combinations whose A row is made of SEGMENTS (rows 4m + q_c of dy) and whose B is the matching
 // stack of tap matrices (prepared per pp, contiguous).  Against the column form (rows 4m + q, N = 9 x 512, K = 1024) the same
 // multiply-adds leave 16 instead of 36 rows of 512 values per window, and the 9-tap sum of col2im happens in the accumulators.
-template <int ELEM, bool GATHER>
-__device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane,
+template <int ELEM, bool GATHER, bool HALO = false>
+__device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x4 (&acc)[8][4], int m0, int n0, int wr, int wc, int lane,
                                                    int wid, char* smem, int m_limit);
 template <int ELEM, int EPI, int ACG = 0, int SEG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
@@ -196,46 +200,47 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
         buf_load_lds16(g, voff[kind][1], soff, base + 1024);
     };
 
-    // ---- fragment reads (row swizzle (row>>1)&7 only depends on lane&31: half tiles start at multiples of 32 rows)
-    const int l31 = lane & 31, kh = lane >> 5, sw = (l31 >> 1) & 7;
-    int ko[4];
+    // ---- fragment reads: 16 rows x 32 k per instruction step, two steps per K tile.  Lane l reads row l&15 of the fragment, logical chunk
+    // 4*ks + (l>>4) (row swizzle (row>>1)&7 only depends on lane&15: fragments start at multiples of 16 rows)
+    const int l15 = lane & 15, kg = lane >> 4, sw = (l15 >> 1) & 7;
+    int ko[2];
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) ko[ks] = ((ks * 2 + kh) ^ sw) << 4;
-    const int a_rd = (wr * 64 + l31) * 128, b_rd = (wc * 32 + l31) * 128;
-    s16x8 af[2][4], bf[2][4];
+    for (int ks = 0; ks < 2; ++ks) ko[ks] = ((ks * 4 + kg) ^ sw) << 4;
+    const int a_rd = (wr * 64 + l15) * 128, b_rd = (wc * 32 + l15) * 128;
+    s16x8 af[4][2], bf[4][2];
     auto read_a = [&](int h, int par) __attribute__((always_inline)) {
         const char* base = smem + ((par << 2) + (h ? 3 : 0)) * HT + a_rd;
 #pragma unroll
-        for (int i = 0; i < 2; ++i)
+        for (int i = 0; i < 4; ++i)
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) af[i][ks] = *reinterpret_cast<const s16x8*>(base + i * 4096 + ko[ks]);
+            for (int ks = 0; ks < 2; ++ks) af[i][ks] = *reinterpret_cast<const s16x8*>(base + i * 2048 + ko[ks]);
     };
     auto read_b = [&](int par) __attribute__((always_inline)) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const char* base = smem + ((par << 2) + 1 + h) * HT + b_rd;
+        for (int j = 0; j < 4; ++j) {                  // column fragment j of the wave: b-half j>>1, its rows (j&1)*16 .. +15
+            const char* base = smem + ((par << 2) + 1 + (j >> 1)) * HT + b_rd + (j & 1) * 2048;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bf[h][ks] = *reinterpret_cast<const s16x8*>(base + ko[ks]);
+            for (int ks = 0; ks < 2; ++ks) bf[j][ks] = *reinterpret_cast<const s16x8*>(base + ko[ks]);
         }
     };
 
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    auto half = [&](int a) __attribute__((always_inline)) {
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
+    auto half = [&](int a) __attribute__((always_inline)) {       // k step outermost: every accumulator sees its K groups in increasing k
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if constexpr (EPI == EPI_STORE_F32T) acc[2 * a + i][j] = mfma32<ELEM>(bf[j][ks], af[i][ks], acc[2 * a + i][j]);
-                    else acc[2 * a + i][j] = mfma32<ELEM>(af[i][ks], bf[j][ks], acc[2 * a + i][j]);
+                for (int j = 0; j < 4; ++j) {
+                    if constexpr (EPI == EPI_STORE_F32T) acc[4 * a + i][j] = mfma16<ELEM>(bf[j][ks], af[i][ks], acc[4 * a + i][j]);
+                    else acc[4 * a + i][j] = mfma16<ELEM>(af[i][ks], bf[j][ks], acc[4 * a + i][j]);
                 }
         SGC_PP_BARRIER();
     };
@@ -286,10 +291,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
     }
     else if constexpr (ACG && EPI == EPI_POOL) {
         if (p.epi_lds) nt_epilogue_pool16<ELEM, true>(p, acc, m0, n0, wr, wc, lane, wid, smem, Mlim);
-        else nt_epilogue<ELEM, EPI, 4, 2, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
+        else nt_epilogue<ELEM, EPI, 8, 4, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
     }
-    else if constexpr (ACG) nt_epilogue<ELEM, EPI, 4, 2, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
-    else nt_epilogue<ELEM, EPI, 4, 2>(p, acc, m0, n0, wr, wc, lane);
+    else if constexpr (ACG) nt_epilogue<ELEM, EPI, 8, 4, true>(p, acc, m0, n0, wr, wc, lane, Mlim);
+    else nt_epilogue<ELEM, EPI, 8, 4>(p, acc, m0, n0, wr, wc, lane);
 }
 
 // conv3 over a window list with the ping-pong block (csrc/kernels_shared.hip): rows = 4 x max_entries, N = 1024, K = 9 x 512
@@ -345,7 +350,7 @@ static int launch_gemm_nt_pp(NtParams p, hipStream_t stream) {
 // LDS-staged bias + ReLU + 2x2 max-pool epilogue of the 8-wave block (conv3 forward: 4.2 GB of f16 + 2.1 GB of routing bytes
 // per launch, + 4.2 GB when the bf16 copy is requested).  In the MFMA C layout a lane owns ONE column, so the direct form
 // issues 2-byte and 1-byte stores (measured 2.0 ms of the 59 ms launch).  Here every wave pools in registers (the four
-// accumulator registers of a window), writes its 32 windows x 64 channels into a private LDS tile (pitch 128 B / 64 B) and
+// accumulator registers of a fragment are one window), writes its 32 windows x 64 channels into a private LDS tile (pitch 128 B / 64 B) and
 // streams complete 128-byte / 64-byte rows out with 16-byte stores.
 // Row pitches 128 B (16-bit tiles) and 64 B (arg-max tile), no padding: the 16-byte read-back covers four rows per 16-lane group and
 // 32 / 16 dwords per row put them on disjoint bank quarters (see EPI_LDS_PITCH in gemm_nt.h; rounds 2-4: 144 / 80 B, two-way conflicts
@@ -356,43 +361,44 @@ constexpr int POOL_EPI_WAVE_BYTES = 32 * POOL_EPI_PY * 2 + 32 * POOL_EPI_PA;    
 // to row dest[prow] (window-major row space) or gather[prow], the routing bytes to gather[prow]; entries >= *gather_n are not written;
 // the raw accumulators of the entries >= raw_first (linear pairs: per-object pre-activations) leave directly from the registers.
 // Rounds 2-4 sent this launch - the step's longest - through the generic epilogue: 96 two- and one-byte stores per lane.
-template <int ELEM, bool GATHER>
-__device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane,
+template <int ELEM, bool GATHER, bool HALO>
+__device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x4 (&acc)[8][4], int m0, int n0, int wr, int wc, int lane,
                                                    int wid, char* smem, int m_limit) {
     __syncthreads();                                   // every wave is done reading operand tiles
     char* ty = smem + wid * POOL_EPI_WAVE_BYTES;
     char* tb = ty + 32 * POOL_EPI_PY;
     char* ta = tb + 32 * POOL_EPI_PY;
-    const int h = lane >> 5, cl = lane & 31;
+    const int g = lane >> 4, cl = lane & 15;
+    constexpr int RB = HALO ? 1 : 0;                        // the bit of the window row that lane>>4 & 1 lands on (frag_row)
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int colw = j * 32 + cl;
+        for (int j = 0; j < 4; ++j) {                       // one fragment = one window per lane: its four registers
+            const int colw = j * 16 + cl;
             const float bias = p.bias ? p.bias[n0 + wc * 64 + colw] : 0.f;
+            float v = acc[i][j][0];
+            int am = 0;
 #pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                float v = acc[i][j][4 * w];
-                int am = 0;
-#pragma unroll
-                for (int q = 1; q < 4; ++q) {
-                    const float t = acc[i][j][4 * w + q];
-                    if (t > v) { v = t; am = q; }
-                }
-                v += bias;
-                if (!(v > 0.f)) { v = 0.f; am = 4; }        // ReLU killed: no gradient path
-                const int row = i * 8 + 2 * w + h;          // window inside the wave's 32
-                if constexpr (GATHER) {
-                    const int prow = (m0 >> 2) + wr * 32 + row;
-                    if (p.raw && prow >= p.raw_first && prow * 4 < m_limit) {
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) p.raw[((long)(prow - p.raw_first) * 4 + q) * p.ldc + n0 + wc * 64 + colw] = acc[i][j][4 * w + q];
-                    }
-                }
-                *reinterpret_cast<u16*>(ty + row * POOL_EPI_PY + colw * 2) = to_elem<ELEM>(v);
-                if (p.C2) *reinterpret_cast<u16*>(tb + row * POOL_EPI_PY + colw * 2) = f32_to_bf16_bits(v);
-                if (p.argmax) *reinterpret_cast<unsigned char*>(ta + row * POOL_EPI_PA + colw) = (unsigned char)am;
+            for (int q = 1; q < 4; ++q) {
+                const float t = acc[i][j][q];
+                if (t > v) { v = t; am = q; }
             }
+            v += bias;
+            if (!(v > 0.f)) { v = 0.f; am = 4; }            // ReLU killed: no gradient path
+            const int row = frag_row<HALO>(i, 4 * g) >> 2;  // window inside the wave's 32
+            if constexpr (GATHER) {
+                const int prow = (m0 >> 2) + wr * 32 + row;
+                if (p.raw && prow >= p.raw_first && prow * 4 < m_limit) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) p.raw[((long)(prow - p.raw_first) * 4 + q) * p.ldc + n0 + wc * 64 + colw] = acc[i][j][q];
+                }
+            }
+            // the two rows that the 32 lanes of one write pass hold (lane>>4 = 0,1 or 2,3) keep their 32-byte quarters swapped against each
+            // other: at a 128-byte pitch they would meet two-way on 8 banks (counted: 1.8 % of the LDS-active cycles of conv3 forward)
+            const int yo = (colw * 2) ^ (((row >> RB) & 1) << 5);
+            *reinterpret_cast<u16*>(ty + row * POOL_EPI_PY + yo) = to_elem<ELEM>(v);
+            if (p.C2) *reinterpret_cast<u16*>(tb + row * POOL_EPI_PY + yo) = f32_to_bf16_bits(v);
+            if (p.argmax) *reinterpret_cast<unsigned char*>(ta + row * POOL_EPI_PA + colw) = (unsigned char)am;
         }
     __builtin_amdgcn_wave_barrier();
     const long prow0 = ((long)m0 >> 2) + wr * 32;
@@ -407,8 +413,9 @@ __device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&a
             orow = p.dest ? p.dest[orow] : p.gather[orow];
         } else if (p.wm_goff) orow = p.wm_goff[orow & 63] + (orow >> 6);      // window-major row space (shared fc1); argmax stays pair-major
         const long o = orow * p.ldc + n0 + wc * 64 + c8 * 8;
-        *reinterpret_cast<uint4*>(out + o) = *reinterpret_cast<const uint4*>(ty + row * POOL_EPI_PY + c8 * 16);
-        if (p.C2) *reinterpret_cast<uint4*>(p.C2 + o) = *reinterpret_cast<const uint4*>(tb + row * POOL_EPI_PY + c8 * 16);
+        const int yo = (c8 * 16) ^ (((row >> RB) & 1) << 5);
+        *reinterpret_cast<uint4*>(out + o) = *reinterpret_cast<const uint4*>(ty + row * POOL_EPI_PY + yo);
+        if (p.C2) *reinterpret_cast<uint4*>(p.C2 + o) = *reinterpret_cast<const uint4*>(tb + row * POOL_EPI_PY + yo);
     }
     if (p.argmax) {
         const int c4 = lane & 3, r16 = lane >> 2;
@@ -435,7 +442,7 @@ __device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x16 (&a
 // GEMM to 36.6 KiB (-43 %), which is what limits that kernel (its load stream and its LDS-read + MFMA loop overlap poorly; staging
 // A on one K tile in nine was measured +10 %).
 // Patch row r = py*18 + px (128 B per row); 16-B chunk swizzle c ^ f(py,px), f = ((px>>1) + 4*(py&1)) & 7, keeps every
-// ds_read_b128 lane group (pixels of windows {0,3,5,6} / {1,2,4,7} on two image rows) conflict-free for all nine taps.
+// ds_read_b128 lane group (the pixels of four windows two apart on two image rows, see the fragment addressing) conflict-free for all nine taps.
 // Per wave and step: phase Y issues the four weight loads of step s+2 (replacing what phase X(s) read) and, in the first
 // taps of a chunk, one piece of the NEXT chunk's patch; it ends with vmcnt(4 or 5): only its own loads may still be in
 // flight, so the weights of step s+1 and every older patch piece have landed.  Phase X issues nothing and has no vmcnt wait.
@@ -547,57 +554,54 @@ __global__ __launch_bounds__(512, 2) void conv16_halo_pp_kernel(const NtParams p
     };
 
     // ---- fragment addressing
-    const int l31 = lane & 31, kh = lane >> 5;
-    int a_row[4], a_px[4], a_py[4];
+    // Row r (0..15) of fragment ii (0..7) of wave row wr is pixel q = r&3 of window (wy, wx) = (4*wr + (ii>>1), 2*(r>>2) + (ii&1)): the two
+    // fragments of a window row take its even and its odd windows (frag_row<true>, gemm_nt.h).  With four CONSECUTIVE windows per fragment the
+    // lane groups of ds_read_b128 ({0-3,12-15,20-27}: windows 0 and 3 at chunk c, 1 and 2 at c^1) meet two-way on six of the nine taps
+    // (kx = 0, 1); with every second window all nine are conflict-free (enumeration of the bank of every lane: profiles/mfma_shape_ab.txt).
+    const int l15 = lane & 15, kg = lane >> 4;
+    const int a_py0 = 8 * wr + ((l15 >> 1) & 1), a_px0 = 4 * (l15 >> 2) + (l15 & 1);      // fragment 0; fragment ii: py + 2*(ii>>1), px + 2*(ii&1)
+    const int a_row0 = a_py0 * 18 + a_px0;
+    const int bsw = (l15 >> 1) & 7;
+    int bko[2];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int m = wr * 128 + i * 32 + l31;
-        const int W = m >> 2, q = m & 3;
-        a_py[i] = 2 * (W >> 3) + (q >> 1);
-        a_px[i] = 2 * (W & 7) + (q & 1);
-        a_row[i] = a_py[i] * 18 + a_px[i];
-    }
-    const int bsw = (l31 >> 1) & 7;
-    int bko[4];
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) bko[ks] = ((ks * 2 + kh) ^ bsw) << 4;
-    const int b_rd = (wc * 32 + l31) * 128;
-    s16x8 af[2][4], bf[2][4];
+    for (int ks = 0; ks < 2; ++ks) bko[ks] = ((ks * 4 + kg) ^ bsw) << 4;
+    const int b_rd = (wc * 32 + l15) * 128;
+    s16x8 af[4][2], bf[4][2];
     auto read_a = [&](int h, int cc, int ky, int kx) __attribute__((always_inline)) {
         const char* ab = abuf0 + (cc & 1) * A_BYTES;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int ii = 2 * h + i;
-            const char* rowp = ab + (a_row[ii] + ky * 18 + kx) * 128;
-            const int f = (((a_px[ii] + kx) >> 1) + 4 * ((a_py[ii] + ky) & 1)) & 7;
+        for (int i = 0; i < 4; ++i) {
+            const int ii = 4 * h + i;
+            const char* rowp = ab + (a_row0 + ((ii >> 1) * 2 + ky) * 18 + (ii & 1) * 2 + kx) * 128;
+            const int f = (((a_px0 + (ii & 1) * 2 + kx) >> 1) + 4 * ((a_py0 + ky) & 1)) & 7;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) af[i][ks] = *reinterpret_cast<const s16x8*>(rowp + (((ks * 2 + kh) ^ f) << 4));
+            for (int ks = 0; ks < 2; ++ks) af[i][ks] = *reinterpret_cast<const s16x8*>(rowp + (((ks * 4 + kg) ^ f) << 4));
         }
     };
     auto read_b = [&](int step) __attribute__((always_inline)) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const char* base = bbuf0 + ((step & 1) * 2 + h) * HT + b_rd;
+        for (int j = 0; j < 4; ++j) {
+            const char* base = bbuf0 + ((step & 1) * 2 + (j >> 1)) * HT + b_rd + (j & 1) * 2048;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bf[h][ks] = *reinterpret_cast<const s16x8*>(base + bko[ks]);
+            for (int ks = 0; ks < 2; ++ks) bf[j][ks] = *reinterpret_cast<const s16x8*>(base + bko[ks]);
         }
     };
 
-    f32x16 acc[4][2];
+    f32x4 acc[8][4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
+    for (int i = 0; i < 8; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j)
+        for (int j = 0; j < 4; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.f;
     auto half = [&](int a) __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
+        for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-            for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 4; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) acc[2 * a + i][j] = mfma32<ELEM>(af[i][ks], bf[j][ks], acc[2 * a + i][j]);
+                for (int j = 0; j < 4; ++j) acc[4 * a + i][j] = mfma16<ELEM>(af[i][ks], bf[j][ks], acc[4 * a + i][j]);
         SGC_PP_BARRIER();
     };
 
@@ -677,12 +681,12 @@ __global__ __launch_bounds__(512, 2) void conv16_halo_pp_kernel(const NtParams p
     if (wr == 0) __builtin_amdgcn_s_barrier();
 
     if constexpr (EPI == EPI_STORE) {
-        if (p.epi_lds) { nt_epilogue_store16<ELEM>(p, acc, m0, n0, wr, wc, lane, wid, smem); return; }
+        if (p.epi_lds) { nt_epilogue_store16<ELEM, false, true>(p, acc, m0, n0, wr, wc, lane, wid, smem); return; }
     }
     if constexpr (EPI == EPI_POOL) {
-        if (p.epi_lds) { nt_epilogue_pool16<ELEM, false>(p, acc, m0, n0, wr, wc, lane, wid, smem, 0); return; }
+        if (p.epi_lds) { nt_epilogue_pool16<ELEM, false, true>(p, acc, m0, n0, wr, wc, lane, wid, smem, 0); return; }
     }
-    nt_epilogue<ELEM, EPI, 4, 2>(p, acc, m0, n0, wr, wc, lane);
+    nt_epilogue<ELEM, EPI, 8, 4, false, true>(p, acc, m0, n0, wr, wc, lane);
 }
 
 template <int ELEM, int EPI>

@@ -69,6 +69,62 @@ __host__ __device__ __forceinline__ int nt_sp_slot_set(int slot, int* pp_out = n
     return py == 0 ? 0 : 1;                            // corner: own pixel (qy, qx) = (py == 3, px == 3) inside the row set of qy
 }
 
+// The LDS-staged 16-byte store epilogue of gemm_nt.h (nt_epilogue_store16: layout of the LDS tile, half swap of odd rows, read-back) for
+// this kernel's 32-row accumulators (v_smfmac C layout: column = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)).
+template <int ELEM, bool MASK = false>
+__device__ __forceinline__ void sp_epilogue_store16(const NtParams& p, f32x16 (&acc)[4][2], int m0, int n0, int wr, int wc, int lane,
+                                                    int wid, char* smem) {
+    __syncthreads();                                   // every wave is done reading operand tiles
+    char* reg = smem + wid * (128 * EPI_LDS_PITCH);
+    const int h = lane >> 5, cl = lane & 31;
+    const bool odd = cl & 1;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = n0 + wc * 64 + j * 32 + cl;
+            const float bias = p.bias ? p.bias[col] : 0.f;
+#pragma unroll
+            for (int rp = 0; rp < 8; ++rp) {
+                float v0 = acc[i][j][2 * rp] + bias, v1 = acc[i][j][2 * rp + 1] + bias;
+                if constexpr (MASK) { v0 *= p.scale; v1 *= p.scale; }
+                const float recv = __shfl_xor(odd ? v0 : v1, 1);
+                const int r0 = ((2 * rp) & 3) + 8 * ((2 * rp) >> 2) + 4 * h;       // row of register 2rp; register 2rp+1 is r0+1
+                const float flo = odd ? recv : v0, fhi = odd ? v1 : recv;
+                unsigned packed;
+                if constexpr (ELEM == ELEM_BF16) packed = f32x2_to_bf16x2_bits(flo, fhi);      // one v_cvt_pk_bf16_f32
+                else packed = (unsigned)to_elem<ELEM>(flo) | ((unsigned)to_elem<ELEM>(fhi) << 16);
+                const int row = i * 32 + r0 + (odd ? 1 : 0);
+                // odd rows keep their two 64-byte halves swapped: the dwords of an (even, odd) lane pair - rows R and R + 1, same column -
+                // then fall on different banks (conflict-free writes), and the read-back below stays conflict-free
+                *reinterpret_cast<unsigned*>(reg + row * EPI_LDS_PITCH + (((j * 32 + (cl & ~1)) * 2) ^ ((row & 1) << 6))) = packed;
+            }
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    u16* out = reinterpret_cast<u16*>(p.C);
+    const int c8 = lane & 7, rsub = lane >> 3;
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const int rowl = it * 8 + rsub;
+        uint4 v = *reinterpret_cast<const uint4*>(reg + rowl * EPI_LDS_PITCH + ((c8 * 16) ^ ((rowl & 1) << 6)));
+        const int row = m0 + wr * 128 + rowl;
+        if (row < p.M) {
+            const long o = (long)row * p.ldc + n0 + wc * 64 + c8 * 8;
+            if constexpr (MASK) {
+                const uint4 f = *reinterpret_cast<const uint4*>(p.mask_src + o);
+                const u16* fh = reinterpret_cast<const u16*>(&f);
+                u16* vh = reinterpret_cast<u16*>(&v);
+#pragma unroll
+                for (int k = 0; k < 8; ++k)
+                    if (!(from_elem<ELEM_F16>(fh[k]) > 0.f)) vh[k] = 0;
+            }
+            *reinterpret_cast<uint4*>(out + o) = v;
+        }
+    }
+}
+
+
 // (Measured and dropped: issuing the global -> LDS pieces INSIDE the matrix slots, between the sparse instructions, instead of in the
 // load sections - 5.10 against 5.10 ms: the load sections are not issue-bound.  What the block waits for is the ARRIVAL of its
 // operands: matrix pipes 37 % busy, LDS 26 % busy (profiles/r05_mid_pmc_*.csv); see the tile walk below.)
@@ -259,7 +315,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt_sp_kernel(const NtSpParams p) 
 
     NtParams q{};
     q.C = p.C; q.M = p.entries; q.ldc = 16 * 512; q.bias = nullptr;
-    nt_epilogue_store16<ELEM_BF16>(q, acc, m0, pp * 512 + nhalf * 256, wr, wc, lane, wid, smem);
+    sp_epilogue_store16<ELEM_BF16>(q, acc, m0, pp * 512 + nhalf * 256, wr, wc, lane, wid, smem);
 }
 
 // ---------------------------------------------------------------------------------------------------- operands
