@@ -308,6 +308,29 @@ int sgc_fc1_gsum_compact(const void* dh1, const int* bbox, const int* sub_idx, c
                          void* gwm, float* part, void* stream);
 int sgc_shared_objects_bg_grad_compact(int n_img, const int* goff, const void* dywm, void* dy_bg, void* stream);
 
+/* Backward of the shared fc1 over the COMPACT row space without the window-major gradient gwm: the two grouped GEMMs read their rows through
+ * a row table from  gsrc [gsrc_rows][4096] bf16 = [the rows of dh1][one zero row][per-object rows, group after group]  (same bits as
+ * sgc_fc1_xrows + the two entries above; csrc/kernels_fc1_rows.hip).
+ *   sgc_window_rows_source       rowsrc [rows]: the source row of every window-major row - X entry e (n_entries of them): gather[e] >> 6;
+ *                                per-object row goff[w] + k, k < xbase[w] - goff[w]: cbase[w] + k; padding rows [gend[w], goff[w+1]):
+ *                                zero_row.  prow_src [n_prow] = prow carried to the source space (pass it with cbase in place of prow / goff
+ *                                and gsrc in place of gwm to sgc_fc1_gsum_compact).  span >= the longest per-object prefix + 255.
+ *                                rowsrc [n_rows] must come preset to zero_row: lists that do not match the host's tables (a scene edited
+ *                                after flattening) leave rows unnamed, and every entry written is held inside the source.
+ *   sgc_fc1_pad_rows_zero        zeroes the padding rows of ywm_bf16 (all that is left of sgc_fc1_xrows)
+ *   sgc_fc1_windows_dgrad_rows   sgc_fc1_windows_dgrad with row r of gwm = row rowsrc[r] of gsrc
+ *   sgc_fc1_windows_wgrad_rows   sgc_fc1_windows_wgrad likewise (rowsrc 16-byte aligned)
+ * Every rowsrc[r] < gsrc_rows <= 262144 (2 GiB: the reach of the blocks' 32-bit offsets); a larger gsrc_rows returns SGC_ERR_ARG, nothing
+ * is launched, and the caller takes the copy path. */
+int sgc_window_rows_source(const int* gather, const int* dest, int n_entries, const int* goff, const int* xbase, const int* gend,
+                           const int* cbase, int zero_row, int span, const int* prow, int n_prow, int n_rows, int* rowsrc, int* prow_src,
+                           void* stream);
+int sgc_fc1_pad_rows_zero(const int* goff, const int* gend, void* ywm_bf16, void* stream);
+int sgc_fc1_windows_dgrad_rows(const void* gsrc, const int* rowsrc, int gsrc_rows, const void* w1pT, const int* tile_group, void* dywm,
+                               int rows, void* stream);
+int sgc_fc1_windows_wgrad_rows(const void* gsrc, const int* rowsrc, int gsrc_rows, const void* ywm_bf16, const int* goff, float* dw, int rows,
+                               void* stream);
+
 /* h1 [n_pairs][4096] f16 = dropout(relu(y[n_pairs][K] * w1p[4096][K]^T + b))   (model.py:148-149; columns of w1p in (window, channel) order) */
 int sgc_fc1_relu(const void* y, const void* w1p, const float* b, void* h1, int n_pairs, int K, int drop_enable, unsigned drop_seed, void* stream);
 

@@ -55,6 +55,7 @@ struct NtParams {
     const int* gather; const int* gather_n;         // AMODE_CONV_GATHER: row m = 4*e + q is pixel q of window gather[e] = image*(S/2)^2 + window;
                                                     // *gather_n = number of list entries (device side; p.M is only the launch bound);
                                                     // EPI_POOL writes entry e to pooled row gather[e]
+                                                    // gemm_nt_pp_rows_kernel: gather [M] is the row table of A (row m = row gather[m] of A)
     // window-major row space of the shared fc1 (csrc/kernels_shared.hip): rows grouped by pooling window, groups padded to 256 rows
     const int* dest;                                // AMODE_CONV_GATHER + EPI_POOL: y / bf16 copy of entry e go to row dest[e] (argmax stays at gather[e])
     const int* wm_goff;                             // EPI_POOL: y / bf16 copy of pooled row r go to row wm_goff[r & 63] + (r >> 6) (argmax stays at r)

@@ -49,6 +49,13 @@ __device__ __forceinline__ void buf_load_lds16(const void* base, int voff, int s
     __builtin_amdgcn_raw_ptr_buffer_load_lds(r, LDS_PTR(lds), 16, voff, soff, 0, 0);
 }
 
+// The same under a record of exactly 2 GiB (the row-table kernels, whose sources may be that large): with 0x7fffffff the last 16 bytes
+// below 2 GiB are out of range - a load of them returns zeros (tests/test_fc1_rows_gather_gpu.py: the last row of a 2 GiB source).
+__device__ __forceinline__ void buf_load_lds16_2g(const void* base, int voff, int soff, void* lds) {
+    const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)0x80000000u, 0x00020000);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, LDS_PTR(lds), 16, voff, soff, 0, 0);
+}
+
 // XCD-aware tile walk: block id -> XCD id%8 (hardware round-robin); each XCD walks a contiguous range of the tile
 // sequence in 4(M) x 8(N) patches, so the 32 blocks resident on one XCD share 4 A panels and 8 B panels through its L2.
 __device__ __forceinline__ void xcd_patch_map(int id, int tiles_m, int tiles_n, int& tm, int& tn, int gm = 4, int gn = 8) {
@@ -104,7 +111,7 @@ __device__ __forceinline__ void nt_epilogue_pool16(const NtParams& p, f32x4 (&ac
 // ACG = 2: one listed-window tile (far_tm, far_tn) in the far form (see above)
 template <int ELEM, int EPI>
 __device__ __forceinline__ void gemm_nt_pp_far_tile(const NtParams& p, char* smem, int far_tm, int far_tn) {
-    constexpr int ACG = 2, SEG = 0;
+    constexpr int ACG = 2, SEG = 0, AROWS = 0;
 #include "gemm_nt_pp_tile.h"
 }
 
@@ -112,6 +119,19 @@ template <int ELEM, int EPI, int ACG = 0, int SEG = 0>
 __global__ __launch_bounds__(512, 2) void gemm_nt_pp_kernel(const NtParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int far_tm = 0, far_tn = 0;             // (ACG = 2 only)
+    constexpr int AROWS = 0;
+#include "gemm_nt_pp_tile.h"
+}
+
+// The plain block with the rows of A named by a row table (p.gather [M]: row m of the product reads row p.gather[m] of p.A; the rows of C
+// are plain): the table enters the per-lane offsets once, before the K loop - main loop, ring, waits and barriers are those above.  Every
+// table entry times the row pitch stays below the 2 GiB the buffer descriptor reaches (the entry point refuses a larger source).  A kernel
+// of its own, so that gemm_nt_pp_kernel keeps its name and its code.
+template <int ELEM, int EPI>
+__global__ __launch_bounds__(512, 2) void gemm_nt_pp_rows_kernel(const NtParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int far_tm = 0, far_tn = 0;
+    constexpr int ACG = 0, SEG = 0, AROWS = 1;
 #include "gemm_nt_pp_tile.h"
 }
 
@@ -202,6 +222,23 @@ static int launch_gemm_nt_pp(NtParams p, hipStream_t stream) {
     const int nb = p.tiles_m * p.tiles_n;
     // the contiguous walk is itself patch-aligned when every XCD's share is a multiple of 32 tiles (fc1 data gradient: 126 x 256
     // tiles, measured 1 % faster than the round-robin patches); otherwise pad, unless the grid is small or the padding > 10 %
+    p.patch_aligned = (nb >= 1024 && (nb & 255) != 0 && grid_aligned * 10 <= nb * 11) ? 1 : 0;
+    SGC_LAUNCH(kern, dim3((unsigned)(p.patch_aligned ? grid_aligned : p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+
+// gemm_nt_pp_rows_kernel (A rows through the row table p.gather) on the grid launch_gemm_nt_pp gives the same shape
+template <int ELEM, int EPI>
+static int launch_gemm_nt_pp_rows(NtParams p, hipStream_t stream) {
+    constexpr int LDS = (EPI == EPI_STORE) ? EPI_LDS_BYTES : 8 * 16384;
+    if (!p.gather) return SGC_ERR_ARG;
+    p.tiles_m = (p.M + 255) / 256;
+    p.tiles_n = p.N / 256;
+    auto kern = gemm_nt_pp_rows_kernel<ELEM, EPI>;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    const int grid_aligned = xcd_patch_grid(p.tiles_m, p.tiles_n);
+    const int nb = p.tiles_m * p.tiles_n;
     p.patch_aligned = (nb >= 1024 && (nb & 255) != 0 && grid_aligned * 10 <= nb * 11) ? 1 : 0;
     SGC_LAUNCH(kern, dim3((unsigned)(p.patch_aligned ? grid_aligned : p.tiles_m * p.tiles_n)), dim3(512), LDS, stream, p);
     SGC_CHECK_LAUNCH();

@@ -1,6 +1,7 @@
 // Body of one output tile of the ping-pong NT block (csrc/gemm_nt_pp.h includes it twice: as the body of gemm_nt_pp_kernel and, ACG = 2,
 // as the tile function of gemm_nt_pp_far_kernel - the same text, so that the kernel every step runs is compiled exactly as before).
-// In scope: template arguments ELEM, EPI, ACG, SEG; const NtParams& p; char* smem; int far_tm, far_tn (ACG = 2: the tile to compute).
+// In scope: template arguments ELEM, EPI, ACG, SEG; const NtParams& p; char* smem; int far_tm, far_tn (ACG = 2: the tile to compute);
+// constexpr int AROWS (gemm_nt_pp_rows_kernel: 1 = row m of A is row p.gather[m] of p.A - a row table, plain rows of C; ACG = SEG = 0).
     constexpr int HT = 16384;                        // half-tile bytes; slot = parity*4 + kind, kind 0 A0, 1 B0, 2 B1, 3 A1
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -59,7 +60,7 @@
 
     // ---- staging sources: wave w writes LDS rows (2w+q)*8 .. +7 of every half tile (q = 0,1), 8 lanes per 128-B row
     const int lrow = lane >> 3, cpos = lane & 7;
-    const u16* const a_blk = ACG ? p.A + img0 * img_elems : p.A + (long)m0 * p.lda;
+    const u16* const a_blk = ACG ? p.A + img0 * img_elems : (AROWS ? p.A : p.A + (long)m0 * p.lda);
     const u16* const b_blk = p.B + b_off + (long)(n_tile * 256) * ldb + (p.tile_group ? (long)p.tile_group[tm] * p.group_stride : 0L);
     int voff[4][2];                                  // byte offsets from a_blk / b_blk
     int far_map[4][2] = {};                          // ACG = 2: maps of the two list entries (lanes 0-31 / 32-63) behind A load 2h + q
@@ -81,6 +82,8 @@
                     far_map[2 * h + q][1] = __builtin_amdgcn_readlane(mp, 32);
                 } else
                 voff[h ? 3 : 0][q] = (int)((conv_row_base(mv, p.lgS, p.Cin) - img0 * img_elems + chunk) * 2);
+            } else if constexpr (AROWS) {              // source rows below 2^31 bytes from p.A (checked by the entry point)
+                voff[h ? 3 : 0][q] = (int)((p.gather[m0 + m] * p.lda + chunk) * 2);
             } else {
                 voff[h ? 3 : 0][q] = (int)((m * p.lda + chunk) * 2);
             }
@@ -116,6 +119,13 @@
                 const int qy = seg_ny == 1 ? (seg_py == 3) : cy, qx = seg_nx == 1 ? (seg_px == 3) : cx;
                 g = a_blk + (long)(qy * 2 + qx) * p.seg_stride;       // wave-uniform: goes into the buffer descriptor
                 soff = (t & 15) << 7;
+            }
+        }
+        if constexpr (AROWS) {
+            if (kind == 0 || kind == 3) {            // offsets reach the last bytes below 2 GiB
+                buf_load_lds16_2g(g, voff[kind][0], soff, base);
+                buf_load_lds16_2g(g, voff[kind][1], soff, base + 1024);
+                return;
             }
         }
         buf_load_lds16(g, voff[kind][0], soff, base);

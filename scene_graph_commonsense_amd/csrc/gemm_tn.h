@@ -32,6 +32,7 @@ struct TnParams {
                                  // BMODE_PATCH: B = [windows][16 pixels of the window's 4 x 4 input patch][Cin] (sgc_windows_im2patch);
                                  // contraction row r = own pixel r&3 of window r>>2, its value for tap (ky, kx) is patch pixel
                                  // (qy + ky, qx + kx): 16 instead of the 36 rows per window of the im2col form, fixed per-lane offsets.
+                                 // gemm_tn_pp_rows_kernel (AROWS): the row table of A - contraction row r is row gather[r] of A.
     const int* goff;             // ping-pong block, grouped form: block -> (group g, tile); the contraction runs over rows goff[g] .. goff[g+1]
                                  // (multiples of 64) and the result goes to columns g*N .. of C (no split-K, splits = number of groups)
 };
@@ -215,183 +216,23 @@ static int launch_gemm_tn_cfg(TnParams p, int splits, int* slabs_out, hipStream_
 // 16(k blocks of 4 rows) x 8(sub-blocks of 16 columns) x 128 B = 16 KiB; A0/A1 hold the column halves {0-63,128-191} /
 // {64-127,192-255} of the M tile (the a-half of both wave rows), B0/B1 the 32-column halves of the four wave columns.
 // Phase X reads A0 and both B halves (32 ds_read_b64_tr_b16), phase Y reads A1 (16).
+// AROWS (gemm_tn_pp_rows_kernel; off everywhere else, where the block compiles as it did without the flag): contraction row r of A is row
+// p.gather[r] of p.A - a row table over the whole K range.  The A base stays p.A and the lane's offset gains table row x pitch.  The four
+// entries of a (wave, q) k block are 16 aligned bytes at a wave-uniform index: one scalar 16-byte read per k block, issued one K tile
+// ahead of its use (scalar reads count on lgkmcnt, which every phase drains; the counted vmcnt waits see the same two loads per half
+// tile), the lane's entry selected by its row kr.  Every entry times the pitch stays below the 2 GiB the descriptor reaches (entry point).
 template <int ELEM, int BMODE, int ACONV>
 __global__ __launch_bounds__(512, 2) void gemm_tn_pp_kernel(const TnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int HT = 16384, BM = 256, BN = 256;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wid >> 2, wc = wid & 3;
-    const int tiles = p.tiles_n * p.tiles_m;
-    int split, tm, tn;
-    if (p.xcd_map) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        split = j / 9;
-        tm = xcd & 3;
-        tn = (j - split * 9) * 2 + (xcd >> 2);
-    } else {
-        split = blockIdx.x / tiles;
-        if (p.xcd_patch) xcd_patch_map(blockIdx.x - split * tiles, p.tiles_m, p.tiles_n, tm, tn);
-        else supertile_map(blockIdx.x - split * tiles, p.tiles_m, p.tiles_n, tm, tn);
-    }
-    const int m0 = tm * BM, n0 = tn * BN;
-    int kt_begin = split * p.ktiles_per_split;
-    int kt_end = kt_begin + p.ktiles_per_split;
-    const int nk_total = p.K >> 6;
-    if (kt_end > nk_total) kt_end = nk_total;
-    if (p.goff) { kt_begin = p.goff[split] >> 6; kt_end = p.goff[split + 1] >> 6; }      // grouped: "split" is the group
-    const int nk = kt_end - kt_begin;
-
-    // ---- staging: one instruction = one k block (4 rows) x 8 sub-blocks of a half tile; wave w owns k blocks 2w, 2w+1
-    const int kr = (lane >> 1) & 3, sb = lane >> 3, c8 = (lane & 1) * 8;
-    int voff[4][2];                                  // kind 0 A0, 1 B0, 2 B1, 3 A1: byte offsets inside a K tile
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        const int kl = (wid * 2 + q) * 4 + kr;
-        long arow;
-        if constexpr (ACONV) arow = conv_row_base(kl, p.lgS, p.CinA) + (long)((1 << p.lgS) + 3) * p.CinA;
-        else arow = (long)kl * p.lda;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            voff[h ? 3 : 0][q] = (int)((arow + m0 + ((sb >> 2) * 8 + h * 4 + (sb & 3)) * 16 + c8) * 2);
-            const int col = n0 + ((sb >> 1) * 4 + h * 2 + (sb & 1)) * 16;      // first column of this lane's 16-column sub-block
-            long b;
-            if constexpr (BMODE == BMODE_CONV) {
-                // the tap is a per-lane quantity: with Cin = 128 a 256-column tile spans two taps, and the last tile of
-                // N = 9*Cin may reach past tap 8 (those columns read tap 8 again and are never stored)
-                const int tap_raw = col / p.Cin;
-                const int tap = tap_raw > 8 ? 8 : tap_raw;
-                const int ky = tap / 3, kx = tap - 3 * ky;
-                b = conv_row_base(kl, p.lgS, p.Cin) + (long)(ky * ((1 << p.lgS) + 2) + kx) * p.Cin + (col - tap_raw * p.Cin);
-            } else if constexpr (BMODE == BMODE_GATHER) {
-                const int tap_raw = col / p.Cin;
-                const int tap = tap_raw > 8 ? 8 : tap_raw;
-                const int ky = tap / 3, kx = tap - 3 * ky;
-                // pixel kr of the window + tap + column; the window's own offset is added per K tile (stage)
-                b = (long)(((kr >> 1) + ky) * 18 + (kr & 1) + kx) * p.Cin + (col - tap_raw * p.Cin);
-            } else if constexpr (BMODE == BMODE_PATCH) {
-                const int tap_raw = col / p.Cin;
-                const int tap = tap_raw > 8 ? 8 : tap_raw;
-                const int ky = tap / 3, kx = tap - 3 * ky;
-                b = (long)((kl >> 2) * 16 + ((kr >> 1) + ky) * 4 + (kr & 1) + kx) * p.Cin + (col - tap_raw * p.Cin);
-            } else {
-                b = (long)kl * p.ldb + col;
-            }
-            voff[1 + h][q] = (int)((b + c8) * 2);
-        }
-    }
-    auto stage = [&](int kind, int it) __attribute__((always_inline)) {      // it = K tile index inside this split
-        char* base = smem + (((it & 1) << 2) + kind) * HT + wid * 2048;
-        const int kt = kt_begin + it;
-        long toff;
-        const u16* g;
-        if (kind == 0 || kind == 3) {
-            if constexpr (ACONV) toff = conv_row_base(kt * 64, p.lgS, p.CinA); else toff = (long)kt * 64 * p.lda;
-            g = p.A + toff;                          // wave-uniform: goes into the buffer descriptor
-        } else {
-            if constexpr (BMODE == BMODE_CONV) toff = conv_row_base(kt * 64, p.lgS, p.Cin);
-            else if constexpr (BMODE == BMODE_PATCH) toff = (long)kt * 16 * 16 * p.Cin;        // 16 windows per K tile, 16 patch pixels each
-            else toff = (long)kt * 64 * p.ldb;
-            g = p.B + toff;                          // (BMODE_GATHER: replaced below by the window's own base)
-        }
-        if constexpr (BMODE == BMODE_GATHER) {
-            if (kind == 1 || kind == 2) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int code = __builtin_amdgcn_readfirstlane(p.gather[__builtin_amdgcn_readfirstlane(kt * 16 + wid * 2 + q)]);
-                    const int W = code & 63;
-                    const u16* gq = p.B + ((long)((code >> 6) * 18 + 2 * (W >> 3)) * 18 + 2 * (W & 7)) * p.Cin;
-                    buf_load_lds16(gq, voff[kind][q], 0, base + q * 1024);
-                }
-                return;
-            }
-        }
-        buf_load_lds16(g, voff[kind][0], 0, base);
-        buf_load_lds16(g, voff[kind][1], 0, base + 1024);
-    };
-
-    // ---- fragment reads: sub-block (wr*4 + i*2 + g) of an A half, (wc*2 + g) of a B half; k blocks ks*4 + kh*2 (+1)
-    const int g = (lane >> 4) & 1, kh = lane >> 5, t16 = lane & 15;
-    const int lane_off = (t16 >> 2) * 32 + (t16 & 3) * 8 + kh * 2048;
-    const int a_rd = (wr * 4 + g) * 128 + lane_off, b_rd = (wc * 2 + g) * 128 + lane_off;
-    s16x8 af[2][4], bf[2][4];
-    auto tr2 = [&](const char* ptr) __attribute__((always_inline)) {
-        const s16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr));
-        const s16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(ptr + 1024));
-        return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
-    };
-    auto read_a = [&](int h, int par) __attribute__((always_inline)) {
-        const char* base = smem + ((par << 2) + (h ? 3 : 0)) * HT + a_rd;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) af[i][ks] = tr2(base + i * 256 + ks * 4096);
-    };
-    auto read_b = [&](int par) __attribute__((always_inline)) {
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            const char* base = smem + ((par << 2) + 1 + h) * HT + b_rd;
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) bf[h][ks] = tr2(base + ks * 4096);
-        }
-    };
-
-    f32x16 acc[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    auto half = [&](int a) __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[2 * a + i][j] = mfma32<ELEM>(af[i][ks], bf[j][ks], acc[2 * a + i][j]);
-        SGC_PP_BARRIER();
-    };
-
-    if (nk > 0) {
-        stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0);
-        if (nk > 1) { stage(0, 1); stage(1, 1); stage(2, 1); SGC_WAIT_VM(8); } else SGC_WAIT_VM(0);
-    }
-    __builtin_amdgcn_s_barrier();
-    if (wr == 1) __builtin_amdgcn_s_barrier();
-    auto tile = [&](int it, int par, auto steady_c) __attribute__((always_inline)) {
-        constexpr bool STEADY = decltype(steady_c)::value;
-        read_a(0, par); read_b(par);
-        if (it + 1 < nk) stage(3, it + 1);
-        SGC_PP_CLOSE(STEADY);
-        half(0);
-        read_a(1, par);
-        if (STEADY) { stage(0, it + 2); stage(1, it + 2); stage(2, it + 2); }
-        SGC_PP_CLOSE(STEADY);
-        half(1);
-    };
-    int it = 0;
-#pragma unroll 1
-    for (; it + 2 < nk; ++it) tile(it, it & 1, std::true_type{});
-#pragma unroll 1
-    for (; it < nk; ++it) tile(it, it & 1, std::false_type{});
-    if (wr == 0) __builtin_amdgcn_s_barrier();
-
-    float* C = p.C + (p.goff ? (long)split * p.N : (long)split * p.slab_stride);
-    const int hh = lane >> 5, cl = lane & 31;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int col = n0 + wc * 64 + j * 32 + cl;
-            if (col >= p.N) continue;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wr * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                C[(long)row * p.ldc + col] = acc[i][j][r];
-            }
-        }
+    constexpr int AROWS = 0;
+#include "gemm_tn_pp_tile.h"
+}
+// plain operands, the rows of A through the row table p.gather (AROWS above); a kernel of its own: gemm_tn_pp_kernel keeps name and code
+template <int ELEM>
+__global__ __launch_bounds__(512, 2) void gemm_tn_pp_rows_kernel(const TnParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int BMODE = BMODE_PLAIN, ACONV = 0, AROWS = 1;
+#include "gemm_tn_pp_tile.h"
 }
 
 template <int ELEM, int BMODE, int ACONV>

@@ -188,6 +188,46 @@ __global__ __launch_bounds__(256) void compact_rows_kernel(const int* __restrict
         __syncthreads();
     }
 }
+// Row table of the fc1 backward (csrc/kernels_fc1_rows.hip): the source row, in the buffer [rows of dh1][one zero row][the per-object rows
+// of group 0, 1, ...], of every row of the compact window-major space.  X entry e: its pair's row of dh1; per-object row k of group w:
+// cbase[w] + k (cbase: first source row of the group's per-object rows); padding rows [gend[w], goff[w+1]): the zero row.  prow_src is
+// prow carried to the same space (what the row sums write through).  One item per X entry, per (group, slot < span) and per prow entry;
+// span >= the longest per-object prefix + 255.  The GEMMs form addresses from this table, so whatever the lists hold - a scene edited
+// after flattening no longer matches the host's counts (tests/test_scene_gpu.py) - every entry names a row of the source: the caller
+// presets the table to the zero row, an X entry is written only to a row inside the space and only with a pair row (< zero_row), and a
+// carried prow stays inside its group's per-object rows.
+__global__ __launch_bounds__(256) void window_rowsrc_kernel(const int* __restrict__ gather, const int* __restrict__ dest, int n_entries,
+                                                            const int* __restrict__ goff, const int* __restrict__ xbase,
+                                                            const int* __restrict__ gend, const int* __restrict__ cbase, int zero_row, int span,
+                                                            const int* __restrict__ prow, int n_prow, int n_rows, int* __restrict__ rowsrc,
+                                                            int* __restrict__ prow_src) {
+    const long n_groups = 64L * span, n_items = n_entries + n_groups + n_prow;
+    for (long it = (long)blockIdx.x * 256 + threadIdx.x; it < n_items; it += (long)gridDim.x * 256) {
+        if (it < n_entries) {
+            const int d = dest[it], src = gather[it] >> 6;
+            if ((unsigned)d < (unsigned)n_rows) rowsrc[d] = (unsigned)src < (unsigned)zero_row ? src : zero_row;
+        } else if (it < n_entries + n_groups) {
+            const long t = it - n_entries;
+            const int w = (int)(t / span), k = (int)(t - (long)w * span);
+            const int lead = xbase[w] - goff[w];
+            if (k < lead) rowsrc[goff[w] + k] = cbase[w] + k;                 // (host tables: consistent among themselves)
+            else if (gend[w] + (k - lead) < goff[w + 1]) rowsrc[gend[w] + (k - lead)] = zero_row;
+        } else {
+            const int i = (int)(it - n_entries - n_groups), w = i & 63;
+            prow_src[i] = cbase[w] + max(0, min(prow[i] - goff[w], xbase[w] - goff[w] - 1));
+        }
+    }
+}
+// the padding rows [gend[g], goff[g+1]) of ywm_bf16 zeroed (they take part in the contraction of the fc1 weight gradient): what is left of
+// fc1_xrows_kernel when the gradient rows are read through the row table.  Block = (group, 4 of its up to 255 padding rows)
+__global__ __launch_bounds__(256) void fc1_pad_rows_zero_kernel(const int* __restrict__ goff, const int* __restrict__ gend, u16* __restrict__ ywm_bf) {
+    const int g = blockIdx.x >> 6, lane = threadIdx.x & 63;
+    const long row = (long)gend[g] + (blockIdx.x & 63) * 4 + (threadIdx.x >> 6);
+    if (row >= goff[g + 1]) return;
+    const uint4 z = make_uint4(0, 0, 0, 0);
+    *reinterpret_cast<uint4*>(ywm_bf + row * 1024 + lane * 8) = z;
+    *reinterpret_cast<uint4*>(ywm_bf + row * 1024 + 512 + lane * 8) = z;
+}
 // rows of the pseudo-pairs' own windows (entries of the window list behind the real pairs'): dest[i] = prow[code - 64 P]
 __global__ void compact_rows_objects_kernel(const int* __restrict__ codes, int n, const int* __restrict__ prow, int P, int* __restrict__ dest) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1061,7 +1101,9 @@ __global__ __launch_bounds__(256) void fc1_gsum_bg_kernel(const float* __restric
 }
 
 // X rows of the window-major gradient: gwm[dest[e]] = dh1[pair of entry e]; and the padding rows of every group are zeroed in gwm
-// and in ywm_bf16 (they take part in the contraction of the weight gradient).
+// and in ywm_bf16 (they take part in the contraction of the weight gradient).  The COPY path of the fc1 backward: without the compact row
+// space, with a source of 2 GiB and more or with TUNING.fc1_rows_gather off; otherwise the GEMMs read dh1's rows through the row table
+// (window_rowsrc_kernel, csrc/kernels_fc1_rows.hip) and only fc1_pad_rows_zero_kernel is left of this pass.
 __global__ __launch_bounds__(256) void fc1_xrows_kernel(const u16* __restrict__ dh, const int* __restrict__ gather, const int* __restrict__ dest,
                                                         int n_entries, const int* __restrict__ goff, const int* __restrict__ gend,
                                                         u16* __restrict__ gwm, u16* __restrict__ ywm_bf, long n_items) {
@@ -1995,6 +2037,22 @@ int sgc_window_rows_compact(const int* bbox, const int* obj_img, int n_obj, int 
 int sgc_window_rows_objects_compact(const int* codes, int n, const int* prow, int n_pairs, int* dest, void* stream) {
     if (n <= 0) return SGC_OK;
     SGC_LAUNCH(compact_rows_objects_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, codes, n, prow, n_pairs, dest);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+int sgc_window_rows_source(const int* gather, const int* dest, int n_entries, const int* goff, const int* xbase, const int* gend,
+                           const int* cbase, int zero_row, int span, const int* prow, int n_prow, int n_rows, int* rowsrc, int* prow_src,
+                           void* stream) {
+    if (n_entries < 0 || span < 256 || n_prow < 0 || zero_row < 0 || n_rows <= 0 || !rowsrc || (n_prow > 0 && (!prow || !prow_src)))
+        return SGC_ERR_ARG;
+    const long items = (long)n_entries + 64L * span + n_prow;
+    SGC_LAUNCH(window_rowsrc_kernel, dim3(grid_cap(items, 256, 65536)), dim3(256), 0, (hipStream_t)stream, gather, dest, n_entries, goff, xbase,
+               gend, cbase, zero_row, span, prow, n_prow, n_rows, rowsrc, prow_src);
+    SGC_CHECK_LAUNCH();
+    return SGC_OK;
+}
+int sgc_fc1_pad_rows_zero(const int* goff, const int* gend, void* ywm_bf16, void* stream) {
+    SGC_LAUNCH(fc1_pad_rows_zero_kernel, dim3(64 * 64), dim3(256), 0, (hipStream_t)stream, goff, gend, (u16*)ywm_bf16);
     SGC_CHECK_LAUNCH();
     return SGC_OK;
 }

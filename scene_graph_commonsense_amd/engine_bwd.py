@@ -130,9 +130,18 @@ class BackwardMixin:
             grads["fc2.bias"] = self._colsum(dpre, Ppad, 512)
 
         # ---- fc2 data gradient
-        dh1 = ws.get("dh1", Ppad * 4096, torch.bfloat16)
-        if Ppad > P:
-            Workspace._zero(dh1[P * 4096:])
+        # (fc1 over the compact window-major rows, ``TUNING.fc1_rows_gather``: dh1 is the head of the buffer the grouped GEMMs gather their
+        #  gradient rows from - [Ppad rows of dh1][one zero row][per-object sums] - so that nothing copies it; ``_fc1_backward_rows``)
+        wm_rows = ctx.shared.get("wm") if (getattr(ctx, "generic", None) is None and getattr(ctx, "shared", None) is not None) else None
+        gsrc = None
+        if fc1_rows_gather_enabled(wm_rows, Ppad):
+            gsrc = ws.get("fc1_gsrc", (Ppad + 1 + wm_rows["objrows"]) * 4096, torch.bfloat16)
+            dh1 = gsrc[:Ppad * 4096]
+            Workspace._zero(gsrc[P * 4096:(Ppad + 1) * 4096])          # the rows behind the last pair and the zero row
+        else:
+            dh1 = ws.get("dh1", Ppad * 4096, torch.bfloat16)
+            if Ppad > P:
+                Workspace._zero(dh1[P * 4096:])
         self._timed("fc2_dgrad", lambda: _lib.check(lib.sgc_fc2_dgrad(_lib.ptr(dpre), _lib.ptr(w["w2mT"]), _lib.ptr(ctx.h1), _lib.ptr(dh1), P, f(scale), st()),
                    "sgc_fc2_dgrad"))
 
@@ -143,7 +152,7 @@ class BackwardMixin:
 
         # ---- fc1
         if getattr(ctx, "shared", None) is not None and ctx.shared.get("wm") is not None:
-            dy = self._fc1_backward_rows(ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook)
+            dy = self._fc1_backward_rows(ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook, gsrc)
         else:
             dy = self._fc1_backward_pairs(ctx, dh1, side, grads, grad_hook)
 
@@ -296,39 +305,66 @@ class BackwardMixin:
         self._timed("fc1_dgrad", lambda: _lib.check(lib.sgc_fc1_dgrad(_lib.ptr(dh1), _lib.ptr(w1pT), _lib.ptr(dy), P, 65536, st()), "sgc_fc1_dgrad"))
         return dy
 
-    def _fc1_backward_rows(self, ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook):
-        """fc1 backward over the window-major rows (``csrc/kernels_shared.hip``): per-object sums of dh1 + one copy of dh1 per X entry,
-        then the grouped weight- and data-gradient GEMMs; returns dywm [rows, 1024] (window-major pooled gradient)."""
+    def _fc1_backward_rows(self, ctx, dh1, sub_csr, obj_csr, img_ptr, side, grads, grad_hook, gsrc=None):
+        """fc1 backward over the window-major rows (``csrc/kernels_shared.hip``): per-object sums of dh1, then the grouped weight- and
+        data-gradient GEMMs; returns dywm [rows, 1024] (window-major pooled gradient).
+        ``gsrc`` (``TUNING.fc1_rows_gather``, compact row space; ``dh1`` is its head): the GEMMs read every gradient row where it lies,
+        through the plan's row table ``rowsrc`` - the pairs' rows of dh1, the per-object sums written behind the zero row, the zero row
+        for the groups' padding (``csrc/kernels_fc1_rows.hip``).  Without it: one copy of dh1's row per X entry into the window-major
+        gradient ``gwm`` first (``sgc_fc1_xrows``).  Same bits either way."""
         lib, w, ws, st, sh = self.lib, self.w, self.scratch, self._st, ctx.shared
         wm = sh["wm"]
-        gwm = ws.get("gwm", wm["rows"] * 4096, torch.bfloat16)
+        gather = gsrc is not None
+        # the row sums write through the row table when the GEMMs read through it: same kernels, other tables
+        gwm = gsrc if gather else ws.get("gwm", wm["rows"] * 4096, torch.bfloat16)
         if wm["prow"] is not None:       # compact row space: rows only inside R_o, the background rows collect the rest (f32 partial sums)
             part = ws.get("gsum_part", int(lib.sgc_fc1_gsum_groups(ctx.n_obj, ctx.n_img)) * 64 * 4096, torch.float32)
             gsum = lambda: _lib.check(lib.sgc_fc1_gsum_compact(
                 _lib.ptr(dh1), _lib.ptr(ctx.bbox), _lib.ptr(ctx.sub_idx), _lib.ptr(ctx.obj_idx), _lib.ptr(sub_csr[0]), _lib.ptr(sub_csr[1]),
-                _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(img_ptr), ctx.n_img, _lib.ptr(wm["goff"]), _lib.ptr(wm["prow"]), ctx.n_obj,
-                _lib.ptr(gwm), _lib.ptr(part), st()), "sgc_fc1_gsum_compact")
+                _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(img_ptr), ctx.n_img, _lib.ptr(wm["cbase"] if gather else wm["goff"]),
+                _lib.ptr(wm["prow_src"] if gather else wm["prow"]), ctx.n_obj, _lib.ptr(gwm), _lib.ptr(part), st()), "sgc_fc1_gsum_compact")
         else:
             gsum = lambda: _lib.check(lib.sgc_fc1_gsum(
                 _lib.ptr(dh1), _lib.ptr(ctx.bbox), _lib.ptr(ctx.sub_idx), _lib.ptr(ctx.obj_idx), _lib.ptr(sub_csr[0]), _lib.ptr(sub_csr[1]),
                 _lib.ptr(obj_csr[0]), _lib.ptr(obj_csr[1]), _lib.ptr(wm["goff"]), ctx.n_obj, _lib.ptr(gwm), st()), "sgc_fc1_gsum")
-        self._timed("fc1_bwd_rows", lambda: (
-            gsum(),
-            _lib.check(lib.sgc_fc1_xrows(_lib.ptr(dh1), _lib.ptr(sh.get("gather_all", sh["gather"])), _lib.ptr(wm["dest"]), wm["E"], _lib.ptr(wm["goff"]),
-                                         _lib.ptr(wm["gend"]), _lib.ptr(gwm), _lib.ptr(sh["ywm_bf"]), st()), "sgc_fc1_xrows")))
+        # (tests and tools read ``scratch.bufs["gwm"]`` / ``["dh1"]`` after a step: on the gather path gwm is what the GEMMs read, built on request)
+        ws.bufs.virtual.pop("gwm", None), ws.bufs.virtual.pop("dh1", None)
+        if gather:                       # all that is left of the X-row pass: the padding rows of ywm_bf take part in the weight gradient
+            gsrc_rows = gsrc.numel() // 4096
+            rowsrc = wm["rowsrc"]
+            ws.bufs.virtual["gwm"] = lambda: gsrc.view(-1, 4096)[rowsrc.long()].reshape(-1)
+            ws.bufs.virtual["dh1"] = lambda: dh1
+            self._timed("fc1_bwd_rows", lambda: (
+                gsum(),
+                _lib.check(lib.sgc_fc1_pad_rows_zero(_lib.ptr(wm["goff"]), _lib.ptr(wm["gend"]), _lib.ptr(sh["ywm_bf"]), st()), "sgc_fc1_pad_rows_zero")))
+        else:
+            self._timed("fc1_bwd_rows", lambda: (
+                gsum(),
+                _lib.check(lib.sgc_fc1_xrows(_lib.ptr(dh1), _lib.ptr(sh.get("gather_all", sh["gather"])), _lib.ptr(wm["dest"]), wm["E"], _lib.ptr(wm["goff"]),
+                                             _lib.ptr(wm["gend"]), _lib.ptr(gwm), _lib.ptr(sh["ywm_bf"]), st()), "sgc_fc1_xrows")))
         dy = ws.get("dywm", wm["rows"] * 1024, torch.bfloat16)
 
         def wgrad():
             with side():
                 dW1p = ws.get("dW1p", 4096 * 65536, torch.float32)
-                self._timed("fc1_wgrad", lambda: _lib.check(lib.sgc_fc1_windows_wgrad(_lib.ptr(gwm), _lib.ptr(sh["ywm_bf"]), _lib.ptr(wm["goff"]),
-                                                                                      _lib.ptr(dW1p), wm["rows"], st()), "sgc_fc1_windows_wgrad"))
+                if gather:
+                    self._timed("fc1_wgrad", lambda: _lib.check(lib.sgc_fc1_windows_wgrad_rows(
+                        _lib.ptr(gsrc), _lib.ptr(wm["rowsrc"]), gsrc_rows, _lib.ptr(sh["ywm_bf"]), _lib.ptr(wm["goff"]), _lib.ptr(dW1p), wm["rows"],
+                        st()), "sgc_fc1_windows_wgrad_rows"))
+                else:
+                    self._timed("fc1_wgrad", lambda: _lib.check(lib.sgc_fc1_windows_wgrad(_lib.ptr(gwm), _lib.ptr(sh["ywm_bf"]), _lib.ptr(wm["goff"]),
+                                                                                          _lib.ptr(dW1p), wm["rows"], st()), "sgc_fc1_windows_wgrad"))
                 self._fc1_finish_wgrad(dW1p, dh1, ctx.Ppad, grads, grad_hook)
 
         def dgrad():
             w1pT = w["w1pT"]                               # deferred copy (Weights): made here, outside the timed launch
-            self._timed("fc1_dgrad", lambda: _lib.check(lib.sgc_fc1_windows_dgrad(_lib.ptr(gwm), _lib.ptr(w1pT), _lib.ptr(wm["tile_group"]),
-                                                                                  _lib.ptr(dy), wm["rows"], st()), "sgc_fc1_windows_dgrad"))
+            if gather:
+                self._timed("fc1_dgrad", lambda: _lib.check(lib.sgc_fc1_windows_dgrad_rows(
+                    _lib.ptr(gsrc), _lib.ptr(wm["rowsrc"]), gsrc_rows, _lib.ptr(w1pT), _lib.ptr(wm["tile_group"]), _lib.ptr(dy), wm["rows"], st()),
+                    "sgc_fc1_windows_dgrad_rows"))
+            else:
+                self._timed("fc1_dgrad", lambda: _lib.check(lib.sgc_fc1_windows_dgrad(_lib.ptr(gwm), _lib.ptr(w1pT), _lib.ptr(wm["tile_group"]),
+                                                                                      _lib.ptr(dy), wm["rows"], st()), "sgc_fc1_windows_dgrad"))
         # GEMM beside GEMM buys nothing on this chip (two ping-pong GEMMs on two streams: 13.5 ms against 13.4 back to back) while an
         # HBM-bound kernel beside a GEMM hides ~40 % of its time (profiles/r03_overlap_microbench.txt).  ``TUNING.gemms_apart``: the
         # weight-gradient GEMM is enqueued AFTER the data-gradient GEMM - ``side()`` orders the side stream behind everything enqueued on

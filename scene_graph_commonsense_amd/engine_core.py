@@ -70,12 +70,27 @@ class Weights(dict):
         return dict.__getitem__(self, key)
 
 
+class _Buffers(dict):
+    """name -> buffer.  ``virtual``: buffers the step no longer keeps but whose contents still exist in another form (the window-major
+    gradient ``gwm`` of the fc1 backward, read through a row table since ``TUNING.fc1_rows_gather``).  Reading such a name builds the
+    tensor at that moment, for inspection by tests and tools; it is not stored, ``in`` / ``get`` do not see it and the step never asks."""
+
+    def __init__(self):
+        super().__init__()
+        self.virtual = {}
+
+    def __missing__(self, name):
+        if name in self.virtual:
+            return self.virtual[name]()
+        raise KeyError(name)
+
+
 class Workspace:
     """Grow-only cache of device buffers keyed by name (no allocation inside the steady-state step)."""
 
     def __init__(self, device):
         self.device = device
-        self.bufs: Dict[str, torch.Tensor] = {}
+        self.bufs: Dict[str, torch.Tensor] = _Buffers()
 
     def get(self, name, numel, dtype, zero=False):
         t = self.bufs.get(name)
@@ -198,6 +213,9 @@ class Tuning:
                                       # side stream's long sparse conv3 weight gradient (the caller's stream waited 2.7 ms for that tail)
     fused_sgd: bool = True            # train_minibatch + optim.FusedSGD: fc1.weight's gradient stays in GEMM order, one pass un-permutes, updates and
                                       # writes the f16 copy (off: transposition + update + transposition; same bits)
+    fc1_rows_gather: bool = True      # fc1 backward over the compact row space: the two grouped GEMMs read their gradient rows through a row table
+                                      # from [dh1][zero row][per-object sums] (off, or a source of 2 GiB and more: one copy of dh1's row per
+                                      # pair-specific window first, sgc_fc1_xrows; same bits)
 
     @classmethod
     def from_env(cls):
@@ -241,6 +259,18 @@ def shared_objects_enabled() -> bool:
     return TUNING.shared_objects
 
 
+FC1_GATHER_ROW_LIMIT = 262144     # rows of 4096 bf16 below 2 GiB: what the 32-bit per-lane offsets of the GEMM blocks' buffer loads reach
+
+
+def fc1_rows_gather_enabled(wm, Ppad) -> bool:
+    """fc1 backward reading its gradient rows through the row table (``TUNING.fc1_rows_gather``): only with the compact row space (the
+    plan then holds ``prow`` and the table ``rowsrc``) and while the source buffer [Ppad pairs + zero row + per-object rows] stays
+    below 2 GiB; otherwise the copy path (``sgc_fc1_xrows`` + the plain entries)."""
+    if not TUNING.fc1_rows_gather or wm is None or wm.get("prow") is None or wm.get("rowsrc") is None:
+        return False
+    return int(Ppad) + 1 + int(wm["objrows"]) < FC1_GATHER_ROW_LIMIT
+
+
 def shared_conv3_enabled(hint=None, n_pairs=0) -> bool:
     """conv3 over shared windows (``TUNING.shared_conv3``).  ``hint`` (the host's count of pair-specific windows,
     ``DeviceScene.shared_windows``): when more than ``TUNING.shared_max_fraction`` of all windows are pair-specific (most boxes
@@ -271,6 +301,7 @@ class _CheckRing:
 
 __all__ = [
     "CP1",
+    "FC1_GATHER_ROW_LIMIT",
     "Dict",
     "ELEM_BF16",
     "ELEM_F16",
@@ -291,6 +322,7 @@ __all__ = [
     "csr_by",
     "ctypes",
     "dataclass",
+    "fc1_rows_gather_enabled",
     "loss_coefficients",
     "math",
     "np",

@@ -150,10 +150,16 @@ class PlanMixin:
         goff, tile_group = window_major_layout(counts, lead)
         # ONE host-to-device copy for the four small tables: group offsets, first X row of every group, group ends, tile -> group
         gend_h = (goff[:64].astype(np.int64) + lead + np.asarray(counts, dtype=np.int64)).astype(np.int32)
+        # (+ with the row table of the fc1 backward, below: ``cbase``, the first source row of every group's per-object rows)
+        gather_rows = compact and TUNING.fc1_rows_gather
+        Ppad = (P + 63) // 64 * 64
+        lead_w = np.broadcast_to(np.asarray(lead, dtype=np.int64), (64,))
+        cbase_h = (Ppad + 1 + np.concatenate([[0], np.cumsum(lead_w)[:-1]])).astype(np.int32) if gather_rows else np.zeros(0, dtype=np.int32)
         tables = np.concatenate([goff.astype(np.int32), np.zeros(3, dtype=np.int32), (goff[:64].astype(np.int64) + lead).astype(np.int32), gend_h,
-                                 np.asarray(tile_group, dtype=np.int32)])          # 68 + 64 + 64 + tiles: every table 16-byte aligned
+                                 np.asarray(tile_group, dtype=np.int32), cbase_h])  # 68 + 64 + 64 + tiles: every table 16-byte aligned
         tab_d = torch.from_numpy(tables).to(dev)
-        goff_d, xbase, gend, tile_group_d = tab_d[:65], tab_d[68:132], tab_d[132:196], tab_d[196:]
+        n_tiles = len(tile_group)
+        goff_d, xbase, gend, tile_group_d = tab_d[:65], tab_d[68:132], tab_d[132:196], tab_d[196:196 + n_tiles]
         prow = None
         if compact:
             prow = torch.empty(n2 * 64, dtype=torch.int32, device=dev)
@@ -197,8 +203,21 @@ class PlanMixin:
                 pair_k = (plan["gather"][:Ec] >> 6).long()
                 first = lambda inc: torch.cat([inc.new_zeros(1), inc[:-1]]).long()
                 dest_conv = dest[torch.arange(Ec, device=dev) - first(plan["incl"])[pair_k] + first(plan["incl_all"])[pair_k]].contiguous()
+        # row table of the fc1 backward (compact row space): the source row of every window-major row in [Ppad rows of dh1][one zero row]
+        # [the groups' per-object rows, compact] - the grouped GEMMs of the backward read their gradient rows through it
+        # (``TUNING.fc1_rows_gather``, csrc/kernels_fc1_rows.hip); ``cbase`` = first source row of every group's per-object rows,
+        # ``prow_src`` = ``prow`` carried to that space (what the row sums write through)
+        rowsrc = cbase = prow_src = None
+        objrows = int(lead_w.sum())
+        if gather_rows:
+            cbase = tab_d[196 + n_tiles:]
+            rowsrc = torch.full((int(goff[64]),), Ppad, dtype=torch.int32, device=dev)     # a row no list entry names reads the zero row
+            prow_src = torch.empty(n2 * 64, dtype=torch.int32, device=dev)
+            _lib.check(self.lib.sgc_window_rows_source(_lib.ptr(gather), _lib.ptr(dest), E, _lib.ptr(goff_d), _lib.ptr(xbase), _lib.ptr(gend),
+                                                       _lib.ptr(cbase), Ppad, int(lead_w.max()) + 256, _lib.ptr(prow), n2 * 64, int(goff[64]), _lib.ptr(rowsrc),
+                                                       _lib.ptr(prow_src), self._st()), "sgc_window_rows_source")
         # ``x_tab`` / ``x_first``: what sgc_fc1_windows_gemm_x16 takes as (goff, n_pseudo) - a group's first X row is x_tab[w] + x_first
-        return dict(goff=goff_d, goff_host=goff, gend=gend, tile_group=tile_group_d, dest=dest, dest_conv=dest_conv,
+        return dict(rowsrc=rowsrc, cbase=cbase, prow_src=prow_src, objrows=objrows, goff=goff_d, goff_host=goff, gend=gend, tile_group=tile_group_d, dest=dest, dest_conv=dest_conv,
                     rows=int(goff[64]), E=E, E_total=Et, n2=n2, prow=prow, xbase=xbase, x_tab=xbase if compact else goff_d,
                     x_first=0 if compact else n2)
 

@@ -22,15 +22,15 @@ ROWS = [
     ("fc1 over the window-major rows: forward products", "engine_fwd.fc1_shared", "sgc_fc1_windows_gemm[_x16]", "MFMA, K = 1024",
      [r"gemm_nt_pp_kernel<0, [78], (0, )?0, 0>", r"gemm_nt_pp_kernel<0, 7"]),
     ("fc1 weight gradient (grouped TN) + conv2 / conv3-object weight gradients", "engine_bwd._fc1_backward_rows / train_backward",
-     "sgc_fc1_windows_wgrad, sgc_conv2_wgrad, sgc_conv3_wgrad[_sparse], sgc_windows_wgrad_patch", "MFMA", [r"gemm_tn_pp_kernel", r"gemm_tn_sp_kernel<0>", r"gemm_tn_kernel"]),
+     "sgc_fc1_windows_wgrad[_rows], sgc_conv2_wgrad, sgc_conv3_wgrad[_sparse], sgc_windows_wgrad_patch", "MFMA", [r"gemm_tn_pp_kernel", r"gemm_tn_pp_rows_kernel", r"gemm_tn_sp_kernel<0>", r"gemm_tn_kernel"]),
     ("fc1 data gradient (grouped NT), conv3 data gradient of the dense tail / objects, fc2, conv2, conv1 GEMMs", "engine_bwd / engine_fwd",
-     "sgc_fc1_windows_dgrad, sgc_windows_dgrad_patches, sgc_conv3_dgrad[_pooled], sgc_fc2_*, sgc_conv2_*, sgc_conv1_tanh", "MFMA",
-     [r"gemm_nt_pp_kernel", r"gemm_nt_kernel", r"conv16_halo"]),
+     "sgc_fc1_windows_dgrad[_rows], sgc_windows_dgrad_patches, sgc_conv3_dgrad[_pooled], sgc_fc2_*, sgc_conv2_*, sgc_conv1_tanh", "MFMA",
+     [r"gemm_nt_pp_kernel", r"gemm_nt_pp_rows_kernel", r"gemm_nt_kernel", r"conv16_halo"]),
     ("pair expansion z = maxpool(relu(U_i + V_j)) next to the pair-specific windows (+ pseudo-pairs)", "engine_fwd.expand", "sgc_pair_expand_dense_windows, sgc_pair_expand_train",
      "vector instructions, then HBM", [r"pair_expand"]),
     ("pair contraction dU_i = sum_j g_ij (both roles)", "engine_bwd.train_backward", "sgc_pair_contract_windows", "vector instructions, then HBM", [r"pair_contract"]),
-    ("fc1 assembly / prefix sums / row sums / X rows", "engine_fwd.fc1_shared, engine_bwd._fc1_backward_rows", "sgc_fc1_assemble*, sgc_fc1_integral, sgc_fc1_gsum, sgc_fc1_xrows",
-     "HBM / L2", [r"fc1_assemble", r"fc1_integral", r"fc1_gsum", r"fc1_xrows", r"fc1_own_rect", r"segment_sum_rows"]),
+    ("fc1 assembly / prefix sums / row sums / X rows", "engine_fwd.fc1_shared, engine_bwd._fc1_backward_rows", "sgc_fc1_assemble*, sgc_fc1_integral, sgc_fc1_gsum, sgc_fc1_xrows / sgc_fc1_pad_rows_zero",
+     "HBM / L2", [r"fc1_assemble", r"fc1_integral", r"fc1_gsum", r"fc1_xrows", r"fc1_pad_rows_zero", r"fc1_own_rect", r"segment_sum_rows"]),
     ("window backward glue: patch sums, packers of the sparse operands, patch copy of the dense tail, un-pool of the tail", "engine_bwd._conv3_backward_shared",
      "sgc_windows_patch_sum2, sgc_windows_dgrad_sparse_pack, (pack inside the sparse wgrad call), sgc_windows_im2patch_f16[_from], sgc_windows_unpool_from", "HBM",
      [r"windows_patch_sum", r"nt_sp_pack", r"windows_sparse_pack", r"windows_im2patch", r"windows_unpool", r"unpool"]),
