@@ -54,10 +54,9 @@ def upload_sg_targets(table, dev):
 
 def scene_boxes(scene, dev) -> torch.Tensor:
     """[n_obj,4] f32 device copy of the scene's raw boxes (x0,x1,y0,y1 as given: the evaluators' boxes), made once and kept on it."""
-    boxes = getattr(scene, "_bbox_raw_f32", None)
-    if boxes is None:
-        boxes = scene._bbox_raw_f32 = torch.from_numpy(np.ascontiguousarray(scene.bbox_raw, dtype=np.float32).reshape(-1, 4)).to(dev)
-    return boxes
+    if scene._bbox_raw_f32 is None:
+        scene._bbox_raw_f32 = torch.from_numpy(np.ascontiguousarray(scene.bbox_raw, dtype=np.float32).reshape(-1, 4)).to(dev)
+    return scene._bbox_raw_f32
 
 
 class RecallMeter:

@@ -23,7 +23,8 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .engine import PairOutputs, RelHeadEngine, make_engine
-from .pairs import DeviceScene, pair_targets_fast, super_multihot
+from .pair_loop import directed_targets
+from .pairs import DeviceScene, super_multihot
 from .synthetic import HeadConfig, predicate_counts
 
 
@@ -321,13 +322,10 @@ class _RelationBase(nn.Module):
             directed_d = directed.to(dev, torch.int32).contiguous()
         elif directed is not None:
             directed_d = torch.from_numpy(np.ascontiguousarray(directed, dtype=np.int32)).to(dev)
-        elif scene.directed is not None and (relationships is None or relationships is scene._rel_src):
-            directed_d = scene.directed
-        elif relationships is not None:            # lists other than the ones the scene was flattened from
-            directed_d = torch.from_numpy(pair_targets_fast(relationships, subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
-        else:
-            raise ValueError("training_step needs relation targets: build the scene from a batch with relationships / subj_or_obj, "
-                             "or pass them (or a directed array) here")
+        else:                                      # fresh: lists other than the ones the scene was flattened from
+            directed_d = directed_targets(scene, relationships, subj_or_obj, "training_step needs relation targets: build the scene from a "
+                                          "batch with relationships / subj_or_obj, or pass them (or a directed array) here",
+                                          fresh=relationships is not None and relationships is not scene._rel_src)
         cw_d = self._class_weight_device(class_weight, dev)
         if loss_coefs is not None:
             if (image_feature_aug is not None or commonsense is not None) and coupled is None:

@@ -198,10 +198,45 @@ def _unfiltered_selection(scene: DeviceScene, iou: torch.Tensor, evaluators) -> 
     return iou.bool() | (per_image < k_max)[image]
 
 
-def feed_evaluators(model, scene: DeviceScene, out, evaluator=None, evaluator_top3=None, overlap=None, directed=None):
+def raw_boxes(scene: DeviceScene) -> torch.Tensor:
+    """[n_obj,4] device copy of ``scene.bbox_raw`` in its own dtype (the boxes as given: what the evaluators and the ranked graphs carry;
+    the kernels' f32 copy is ``metrics.scene_boxes``), made once and kept on the scene."""
+    if scene._bbox_raw_d is None:
+        scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(scene.bbox.device)
+    return scene._bbox_raw_d
+
+
+def directed_targets(scene: DeviceScene, relationships, subj_or_obj, needs: str, fresh: bool = False) -> torch.Tensor:
+    """[P] int32 device: the directed target of every pair - what ``flatten_scene`` (or ``assign_sgdet_targets``) left on the scene, else
+    (or with ``fresh``: the lists are not the ones the scene was flattened from) derived from the lists and uploaded.  ``needs``: the
+    caller's ``ValueError`` text when there are neither."""
+    if scene.directed is not None and not fresh:
+        return scene.directed
+    if relationships is None:
+        raise ValueError(needs)
+    return torch.from_numpy(pair_targets_fast(relationships, subj_or_obj, scene.pidx).astype(np.int32)).to(scene.bbox.device)
+
+
+def pair_cat_confidence(scene: DeviceScene, per_image, needs: str) -> torch.Tensor:
+    """[P] f32 device: subject + object category confidence of every pair from per-image lists of per-object confidences
+    (``evaluator.py:129-130``); ``needs``: the caller's ``ValueError`` text when they do not hold one value per object."""
+    conf_obj = torch.cat([torch.as_tensor(c).reshape(-1).to(scene.bbox.device, torch.float32) for c in per_image])
+    if int(conf_obj.numel()) != int(scene.cats.numel()):
+        raise ValueError(needs)
+    return conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+
+
+_FEED_NEEDS_TARGETS = "the evaluator feed needs relation targets: flatten the scene from a batch with relationships / subj_or_obj"
+_SGDET_NEEDS_CONFIDENCES = "cat_pred_confidence must hold one value per predicted object"
+
+
+def feed_evaluators(model, scene: DeviceScene, out, evaluator=None, evaluator_top3=None, overlap=None, directed=None, *,
+                    cat_confidence=None, targets: bool = True):
     """Append one minibatch to the Recall@K evaluators in the reference's candidate order (``evaluator.py:231-246``).
     ``overlap`` = [P] uint8 device mask of the overlap filter (``train_test.py:403-410``): direction-steps in which no image's
     boxes overlap are skipped entirely (no candidates, no targets); ``None`` = no filter (``training()``, ``:209``).
+    SGDET / SGCLS: ``cat_confidence`` [P] (``pair_cat_confidence``) is added to every candidate of the pair and ``targets=False``
+    appends no relation targets (they come from ``Evaluator.accumulate_target``).
     Everything stays on the device (the pair tables of the scene are device tensors); the only host synchronisation is the size
     of the kept set.  Returns ``included`` [P] bool device tensor (pairs of the kept steps)."""
     cfg = model.head_config()
@@ -209,26 +244,23 @@ def feed_evaluators(model, scene: DeviceScene, out, evaluator=None, evaluator_to
     included, any_overlap = _step_filter(scene, overlap)
     if evaluator is None and evaluator_top3 is None:
         return included
-    if directed is None:
-        if scene.directed is None:
-            raise ValueError("the evaluator feed needs relation targets: flatten the scene from a batch with relationships / subj_or_obj")
-        directed = scene.directed
+    if targets and directed is None:
+        directed = directed_targets(scene, None, None, _FEED_NEEDS_TARGETS)
     iou = overlap if overlap is not None else torch.ones(scene.n_pairs, dtype=torch.uint8, device=dev)
     sel = torch.nonzero(included).flatten()
     sizes = (scene.step_ptr[1:] - scene.step_ptr[:-1])[any_overlap]            # pairs per kept direction-step, in order
     which = scene.image.long()[sel]
-    tgt = torch.as_tensor(directed).to(dev)[sel].long()
+    tgt = torch.as_tensor(directed).to(dev)[sel].long() if targets else None
     sub, obj = scene.sub_idx.long()[sel], scene.obj_idx.long()[sel]
     scat, ocat = scene.cats[sub], scene.cats[obj]
-    raw = getattr(scene, "_bbox_raw_d", None)
-    if raw is None:
-        raw = scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(dev)
+    raw = raw_boxes(scene)
     sbox, obox = raw[sub], raw[obj]
     logsig = torch.log(torch.sigmoid(out.connectivity[sel]))
     iou_sel = iou[sel].bool()
     if evaluator is not None:
         evaluator.accumulate_candidates(which, out.cand_conf[sel], out.cand_pred[sel], tgt, logsig, scat, ocat, sbox, obox,
-                                        iou_mask=iou_sel, call_sizes=sizes)
+                                        iou_mask=iou_sel, call_sizes=sizes,
+                                        cat_confidence=None if cat_confidence is None else cat_confidence[sel])
     if evaluator_top3 is not None and cfg.hierarchical:
         conf3 = out.cand_conf[sel].max(dim=1)[0]
         evaluator_top3.accumulate_candidates(which, conf3, out.cand_pred[sel], tgt, logsig, scat, ocat, sbox, obox, iou_mask=iou_sel)
@@ -272,6 +304,65 @@ class MinibatchLookahead:
         return cur
 
 
+# ------------------------------------------------------------------------------------------------ the six evaluation entry points
+# share one prologue (``_scene_of``, ``_filters``, the table helpers above) and one forward (``_scoring_forward``).  In all but
+# ``evaluate_minibatch`` every upload and per-scene table is made BEFORE the forward is enqueued and nothing after it synchronises
+# with the host.  Which ``model.last_*`` attributes a call touches is part of its contract (train_test.py reads ``last_outputs is None``
+# as a signal, bench.py reads ``last_outputs`` and ``last_image_groups``):
+#
+#   call                          last_image_groups   last_outputs   last_connectivity_stats
+#   evaluate_minibatch            set                 untouched      set: None, or the stats when select is None and the scene has raw targets
+#   evaluate_sgdet_minibatch      set                 untouched      untouched
+#   predict_scene_graphs          set                 set            untouched
+#   score_minibatch               set                 set            as evaluate_minibatch
+#   score_sgdet_minibatch         set                 set            untouched
+#   mine_commonsense_candidates   set                 set            untouched
+def _scoring_forward(model, cfg, batch, scene, iou, select, workspace_budget):
+    """The fused forward over the scene's pairs, in image groups when the minibatch exceeds the workspace budget (16 images x 100+
+    detections).  The only place of the evaluation path that plans image groups, runs the forward or sets ``model.last_image_groups``."""
+    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
+    if len(groups) > 1:
+        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
+    else:
+        out = model.forward_pairs(scene, iou_mask=iou, select=select)
+    model.last_image_groups = groups
+    return out
+
+
+def _scene_of(model, batch, scene: Optional[DeviceScene] = None):
+    """(cfg, device, scene): the caller's scene, else the batch flattened on the model's device."""
+    cfg = model.head_config()
+    dev = next(model.parameters()).device
+    return cfg, dev, scene if scene is not None else flatten_scene(cfg, batch, dev)
+
+
+def _filters(scene: DeviceScene, overlap_filtering: bool, skip_filtered: bool, rankers, *, steps: bool = True):
+    """(iou, included, select): the overlap mask [P] u8 or None (filter off); the pairs of the kept steps [P] bool or None (filter off,
+    or ``steps=False``: the evaluator feed decides them itself, after the forward); the pairs to compute [P] bool when both flags
+    are set (``rankers``: the evaluators or the meter whose ``top_k`` bounds what a filtered pair can reach), else None."""
+    iou = overlap_mask(scene) if overlap_filtering else None
+    included = _step_filter(scene, iou)[0] if (overlap_filtering and steps) else None
+    select = _unfiltered_selection(scene, iou, rankers) if (skip_filtered and overlap_filtering) else None
+    return iou, included, select
+
+
+def _bitmaps_of(model, commonsense, dev):
+    """``commonsense`` as a ``commonsense.TripletBitmaps``: one passes through, (aligned, violated) collections are converted."""
+    from .commonsense import TripletBitmaps
+    if commonsense is None or isinstance(commonsense, TripletBitmaps):
+        return commonsense
+    return model._commonsense_bitmaps(commonsense, dev)
+
+
+def _connectivity_stats(model, scene: DeviceScene, out, directed, included, select):
+    """Sets ``model.last_connectivity_stats``: the counters of ``evaluate_one_direction`` over the kept steps, None when pairs were
+    skipped or the scene has no raw targets."""
+    model.last_connectivity_stats = None
+    if select is None and scene.raw_target is not None:
+        model.last_connectivity_stats = model.engine().connectivity_stats(
+            out.connectivity, directed, scene.raw_target, None if included is None else included.to(torch.uint8))
+
+
 def evaluate_minibatch(model, batch, evaluator=None, evaluator_top3=None, overlap_filtering: bool = True,
                        scene: Optional[DeviceScene] = None, skip_filtered: bool = False, workspace_budget: Optional[float] = None,
                        while_running=None):
@@ -286,30 +377,16 @@ def evaluate_minibatch(model, batch, evaluator=None, evaluator_top3=None, overla
     would need more is scored in consecutive image groups (``plan_image_groups``) - same outputs, same evaluator feed.
     ``while_running``: called once, with no arguments, after the forward has been enqueued and before the evaluator feed's first
     host synchronisation - the place for host work that does not depend on this minibatch (``MinibatchLookahead.fetch_next``)."""
-    cfg = model.head_config()
-    dev = next(model.parameters()).device
-    if scene is None:
-        scene = flatten_scene(cfg, batch, dev)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    select = None
-    if skip_filtered and overlap_filtering:
-        select = _unfiltered_selection(scene, iou, (evaluator, evaluator_top3))
-    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
-    if len(groups) > 1:
-        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
-    else:
-        out = model.forward_pairs(scene, iou_mask=iou, select=select)
-    model.last_image_groups = groups
+    cfg, _, scene = _scene_of(model, batch, scene)
+    iou, _, select = _filters(scene, overlap_filtering, skip_filtered, (evaluator, evaluator_top3), steps=False)
+    out = _scoring_forward(model, cfg, batch, scene, iou, select, workspace_budget)
     if while_running is not None:
         while_running()
-    directed_d = scene.directed
-    if directed_d is None:
-        directed_d = torch.from_numpy(pair_targets_fast(batch.relationships, batch.subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
+    # the one caller that derives its targets AFTER the forward is enqueued: ``while_running`` must run with the device busy and before
+    # anything here waits for it (MinibatchLookahead)
+    directed_d = directed_targets(scene, batch.relationships, batch.subj_or_obj, _FEED_NEEDS_TARGETS)
     included = feed_evaluators(model, scene, out, evaluator, evaluator_top3, overlap=iou, directed=directed_d)
-    model.last_connectivity_stats = None
-    if select is None and scene.raw_target is not None:
-        model.last_connectivity_stats = model.engine().connectivity_stats(out.connectivity, directed_d, scene.raw_target,
-                                                                          included.to(torch.uint8))
+    _connectivity_stats(model, scene, out, directed_d, included, select)
     return scene, out, included.cpu().numpy(), directed_d.cpu().numpy().astype(np.int64)
 
 
@@ -318,7 +395,6 @@ def _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, 
     (``evaluate.py:375-444``) - the batch construction ``evaluate_sgdet_minibatch`` and ``score_sgdet_minibatch`` share."""
     from .synthetic import SceneBatch
     cfg = model.head_config()
-    dev = next(model.parameters()).device
     if len(categories_pred) != int(image_feature.shape[0]):
         raise ValueError("one predicted-object list per image is required (the reference drops the whole minibatch otherwise)")
     sp = None
@@ -328,18 +404,8 @@ def _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, 
         sp = [[torch.as_tensor(sub2super[int(c)]) for c in cats.tolist()] for cats in categories_pred]
     batch = SceneBatch(image_feature, image_depth, [b.detach().float().cpu() for b in bbox_pred],
                        [c.detach().cpu().long() for c in categories_pred], sp, None, None)
-    return cfg, dev, batch, flatten_scene(cfg, batch, dev)
-
-
-def _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget):
-    """The fused forward over the predicted objects' pairs, in image groups when the minibatch exceeds the workspace budget."""
-    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))       # 16 images x 100+ detections: image groups
-    if len(groups) > 1:
-        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
-    else:
-        out = model.forward_pairs(scene, iou_mask=iou, select=select)
-    model.last_image_groups = groups
-    return out
+    _, dev, scene = _scene_of(model, batch)
+    return cfg, dev, batch, scene
 
 
 def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred, cat_pred_confidence, bbox_pred, evaluator,
@@ -352,20 +418,11 @@ def evaluate_sgdet_minibatch(model, image_feature, image_depth, categories_pred,
     (relationships, subj_or_obj, categories_target, bbox_target) sets the ground truth through ``match_target_sgd`` +
     ``Evaluator.accumulate_target``; call ``evaluator.compute(per_class, predcls=False)`` afterwards.
     ``sub2super``: the ``sub2super_cat_dict`` (VG hierarchical label vectors)."""
-    cfg, dev, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    select = _unfiltered_selection(scene, iou, (evaluator,)) if (skip_filtered and overlap_filtering) else None
-    out = _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget)
-    included, any_overlap = _step_filter(scene, iou)
-    sel = torch.nonzero(included).flatten()
-    sub, obj = scene.sub_idx.long()[sel], scene.obj_idx.long()[sel]
-    conf_obj = torch.cat([c.reshape(-1).to(dev, torch.float32) for c in cat_pred_confidence])
-    raw = torch.from_numpy(scene.bbox_raw).to(dev)
-    iou_sel = iou[sel].bool() if iou is not None else torch.ones(int(sel.numel()), dtype=torch.bool, device=dev)
-    evaluator.accumulate_candidates(scene.image.long()[sel], out.cand_conf[sel], out.cand_pred[sel], None,
-                                    torch.log(torch.sigmoid(out.connectivity[sel])), scene.cats[sub], scene.cats[obj], raw[sub], raw[obj],
-                                    iou_mask=iou_sel, call_sizes=(scene.step_ptr[1:] - scene.step_ptr[:-1])[any_overlap],
-                                    cat_confidence=conf_obj[sub] + conf_obj[obj])
+    cfg, _, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
+    iou, _, select = _filters(scene, overlap_filtering, skip_filtered, (evaluator,), steps=False)
+    out = _scoring_forward(model, cfg, batch, scene, iou, select, workspace_budget)
+    cat_conf = pair_cat_confidence(scene, cat_pred_confidence, _SGDET_NEEDS_CONFIDENCES)
+    included = feed_evaluators(model, scene, out, evaluator, overlap=iou, cat_confidence=cat_conf, targets=False)
     if targets is not None:
         cs, co, bs, bo, rt = match_target_sgd(*targets)
         evaluator.accumulate_target(rt, cs, co, bs, bo)
@@ -389,17 +446,11 @@ def score_sgdet_minibatch(model, image_feature, image_depth, categories_pred, ca
         raise ValueError("the metrics need the ground truth: targets=(relationships, subj_or_obj, categories_target, bbox_target)")
     cfg, dev, batch, scene = _sgdet_scene(model, image_feature, image_depth, categories_pred, bbox_pred, sub2super)
     table = upload_sg_targets(sg_target_table(*targets), dev)
-    conf_obj = torch.cat([torch.as_tensor(c).reshape(-1).to(dev, torch.float32) for c in cat_pred_confidence])
-    if int(conf_obj.numel()) != int(scene.cats.numel()):
-        raise ValueError("cat_pred_confidence must hold one value per predicted object")
-    cat_conf = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+    cat_conf = pair_cat_confidence(scene, cat_pred_confidence, _SGDET_NEEDS_CONFIDENCES)
     image_pair_lists(scene)                         # the per-scene tables of the update, made (and uploaded) once, before the forward
     scene_boxes(scene, dev)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    included = _step_filter(scene, iou)[0] if overlap_filtering else None
-    select = _unfiltered_selection(scene, iou, (meter,)) if (skip_filtered and overlap_filtering) else None
-    out = _sgdet_forward(model, cfg, batch, scene, iou, select, workspace_budget)
-    model.last_outputs = out
+    iou, included, select = _filters(scene, overlap_filtering, skip_filtered, (meter,))
+    model.last_outputs = out = _scoring_forward(model, cfg, batch, scene, iou, select, workspace_budget)
     meter.update(scene, out, overlap=iou, included=included, sg_targets=table, cat_conf=cat_conf)
     return scene, out
 
@@ -407,12 +458,11 @@ def score_sgdet_minibatch(model, image_feature, image_depth, categories_pred, ca
 def image_pair_lists(scene: DeviceScene):
     """(ptr [B+1] int32, list [P] int32) on the device: the pair rows of every image in ascending order - the per-image view of
     the step-major pair order that ``sgc_scene_graph_topk`` walks.  Derived once per scene (one stable device sort) and kept on it."""
-    cached = getattr(scene, "_image_pairs", None)
-    if cached is None:
+    if scene._image_pairs is None:
         n = np.asarray(scene.num_objects, dtype=np.int64)
         ptr = torch.from_numpy(np.concatenate([[0], np.cumsum(n * (n - 1))]).astype(np.int32)).to(scene.bbox.device)
-        cached = scene._image_pairs = (ptr, torch.sort(scene.image, stable=True)[1].to(torch.int32))
-    return cached
+        scene._image_pairs = (ptr, torch.sort(scene.image, stable=True)[1].to(torch.int32))
+    return scene._image_pairs
 
 
 def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool = True, commonsense=None, cat_confidence=None,
@@ -427,33 +477,14 @@ def predict_scene_graphs(model, batch, top_k: int = 20, overlap_filtering: bool 
     takes them (subject + object confidence is added to every candidate of the pair).  A minibatch over ``workspace_budget`` is
     scored in image groups like ``evaluate_minibatch``.  Everything the ranking needs besides the forward's outputs is put on the
     device BEFORE the forward is enqueued; nothing after it synchronises with the host."""
-    from .commonsense import TripletBitmaps
     from .scene_graph import attach_objects, rank_scene_graphs
-    cfg = model.head_config()
-    dev = next(model.parameters()).device
-    if scene is None:
-        scene = flatten_scene(cfg, batch, dev)
+    cfg, dev, scene = _scene_of(model, batch, scene)
     ptr, lst = image_pair_lists(scene)
-    raw = getattr(scene, "_bbox_raw_d", None)
-    if raw is None:
-        raw = scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(dev)
-    bitmaps = commonsense
-    if commonsense is not None and not isinstance(commonsense, TripletBitmaps):
-        bitmaps = model._commonsense_bitmaps(commonsense, dev)
-    cat_conf = None
-    if cat_confidence is not None:
-        conf_obj = torch.cat([torch.as_tensor(c).reshape(-1).to(dev, torch.float32) for c in cat_confidence])
-        if int(conf_obj.numel()) != int(scene.cats.numel()):
-            raise ValueError("cat_confidence must hold one value per object")
-        cat_conf = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
-    iou = overlap_mask(scene) if overlap_filtering else None
-    included = _step_filter(scene, iou)[0] if overlap_filtering else None
-    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
-    if len(groups) > 1:
-        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, None)
-    else:
-        out = model.forward_pairs(scene, iou_mask=iou)
-    model.last_image_groups, model.last_outputs = groups, out
+    raw = raw_boxes(scene)
+    bitmaps = _bitmaps_of(model, commonsense, dev)
+    cat_conf = None if cat_confidence is None else pair_cat_confidence(scene, cat_confidence, "cat_confidence must hold one value per object")
+    iou, included, _ = _filters(scene, overlap_filtering, False, ())
+    model.last_outputs = out = _scoring_forward(model, cfg, batch, scene, iou, None, workspace_budget)
     # torch's own log(sigmoid(x)), as the evaluator feed forms it: the ranked scores are bit for bit the evaluator's confidences
     logsig = torch.log(torch.sigmoid(out.connectivity))
     graphs = rank_scene_graphs(out.cand_conf, out.cand_pred, logsig, ptr, top_k=top_k, pair_list=lst, slot_major=False, cat_conf=cat_conf,
@@ -474,36 +505,17 @@ def score_minibatch(model, batch, meter, overlap_filtering: bool = True, scene: 
     is put on the device BEFORE the forward is enqueued; nothing after it synchronises with the host - the numbers are the caller's
     ``meter.compute*()``.  PredCLS; the SGDET / SGCLS counterpart is ``score_sgdet_minibatch``.
     Returns (scene, outputs)."""
-    from .commonsense import TripletBitmaps
     from .metrics import scene_boxes
-    cfg = model.head_config()
-    dev = next(model.parameters()).device
-    if scene is None:
-        scene = flatten_scene(cfg, batch, dev)
-    directed = scene.directed
-    if directed is None:
-        if getattr(batch, "relationships", None) is None:
-            raise ValueError("the metrics need relation targets: a batch with relationships / subj_or_obj")
-        directed = torch.from_numpy(pair_targets_fast(batch.relationships, batch.subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
+    cfg, dev, scene = _scene_of(model, batch, scene)
+    directed = directed_targets(scene, getattr(batch, "relationships", None), getattr(batch, "subj_or_obj", None),
+                                "the metrics need relation targets: a batch with relationships / subj_or_obj")
     image_pair_lists(scene)                         # the two per-scene tables of the update, made (and uploaded) once, before the forward
     scene_boxes(scene, dev)
-    bitmaps = commonsense
-    if commonsense is not None and not isinstance(commonsense, TripletBitmaps):
-        bitmaps = model._commonsense_bitmaps(commonsense, dev)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    included = _step_filter(scene, iou)[0] if overlap_filtering else None
-    select = _unfiltered_selection(scene, iou, (meter,)) if (skip_filtered and overlap_filtering) else None
-    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
-    if len(groups) > 1:
-        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, select)
-    else:
-        out = model.forward_pairs(scene, iou_mask=iou, select=select)
-    model.last_image_groups, model.last_outputs = groups, out
+    bitmaps = _bitmaps_of(model, commonsense, dev)
+    iou, included, select = _filters(scene, overlap_filtering, skip_filtered, (meter,))
+    model.last_outputs = out = _scoring_forward(model, cfg, batch, scene, iou, select, workspace_budget)
     meter.update(scene, out, overlap=iou, included=included, commonsense=bitmaps, top3=cfg.dataset == "vg", directed=directed)
-    model.last_connectivity_stats = None
-    if select is None and scene.raw_target is not None:
-        model.last_connectivity_stats = model.engine().connectivity_stats(
-            out.connectivity, directed, scene.raw_target, None if included is None else included.to(torch.uint8))
+    _connectivity_stats(model, scene, out, directed, included, select)
     return scene, out
 
 
@@ -518,27 +530,13 @@ def mine_commonsense_candidates(model, batch, top_k: int = 10, overlap_filtering
     nothing after the forward synchronises with the host."""
     from .evaluator import related_topk
     from .scene_graph import MinedCandidates, rank_scene_graphs
-    cfg = model.head_config()
-    dev = next(model.parameters()).device
-    if scene is None:
-        scene = flatten_scene(cfg, batch, dev)
-    directed = scene.directed
-    if directed is None:
-        if getattr(batch, "relationships", None) is None:
-            raise ValueError("the candidate mining needs relation targets: a batch with relationships / subj_or_obj")
-        directed = torch.from_numpy(pair_targets_fast(batch.relationships, batch.subj_or_obj, scene.pidx).astype(np.int32)).to(dev)
+    cfg, dev, scene = _scene_of(model, batch, scene)
+    directed = directed_targets(scene, getattr(batch, "relationships", None), getattr(batch, "subj_or_obj", None),
+                                "the candidate mining needs relation targets: a batch with relationships / subj_or_obj")
     ptr, lst = image_pair_lists(scene)
-    raw = getattr(scene, "_bbox_raw_d", None)
-    if raw is None:
-        raw = scene._bbox_raw_d = torch.from_numpy(scene.bbox_raw).to(dev)
-    iou = overlap_mask(scene) if overlap_filtering else None
-    included = _step_filter(scene, iou)[0] if overlap_filtering else None
-    groups = plan_image_groups(cfg, batch, False, _budget(model, workspace_budget))
-    if len(groups) > 1:
-        out = forward_pairs_chunked(model, cfg, batch, scene, groups, iou, None)
-    else:
-        out = model.forward_pairs(scene, iou_mask=iou)
-    model.last_image_groups, model.last_outputs = groups, out
+    raw = raw_boxes(scene)
+    iou, included, _ = _filters(scene, overlap_filtering, False, ())
+    model.last_outputs = out = _scoring_forward(model, cfg, batch, scene, iou, None, workspace_budget)
     P, B, K = scene.n_pairs, int(ptr.numel()) - 1, int(top_k)
     g = rank_scene_graphs(out.cand_conf, out.cand_pred, torch.zeros(P, device=dev), ptr, top_k=K, pair_list=lst, slot_major=False,
                           mask=iou, included=included, sub_idx=scene.sub_idx, obj_idx=scene.obj_idx, cats=scene.cats)   # x + 0 is exact

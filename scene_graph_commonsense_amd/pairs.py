@@ -121,7 +121,10 @@ class DeviceScene:
 
     def __init__(self, **kw):
         self._pidx = None
-        self.directed = None          # [P] int32 device: directed target per pair (-1 = not connected), when targets were given
+        # device tables derived from the scene on first use, each by ONE accessor: pair_loop.image_pair_lists (per-image pair rows),
+        # pair_loop.raw_boxes (bbox_raw in its own dtype: the evaluators' boxes), metrics.scene_boxes (bbox_raw as f32: the kernels')
+        self._image_pairs = self._bbox_raw_d = self._bbox_raw_f32 = None
+        self.directed = None         # [P] int32 device: directed target per pair (-1 = not connected), when targets were given
         self.raw_target = None        # [P] int32 device: stored predicate of the unordered pair (either direction)
         self.__dict__.update(kw)
 

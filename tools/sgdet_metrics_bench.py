@@ -32,8 +32,8 @@ sys.path.insert(0, REPO)
 from scene_graph_commonsense_amd.evaluator import Evaluator                            # noqa: E402
 from scene_graph_commonsense_amd.metrics import RecallMeter                            # noqa: E402
 from scene_graph_commonsense_amd.model import BayesianRelationClassifier               # noqa: E402
-from scene_graph_commonsense_amd.pair_loop import (_sgdet_forward, _sgdet_scene, evaluate_sgdet_minibatch, overlap_mask,  # noqa: E402
-                                                   score_sgdet_minibatch)
+from scene_graph_commonsense_amd.pair_loop import (_scoring_forward, _sgdet_scene, evaluate_sgdet_minibatch, overlap_mask,  # noqa: E402
+                                                   pair_cat_confidence, score_sgdet_minibatch)
 from scene_graph_commonsense_amd.synthetic import HeadConfig, default_sub2super, make_scene_batch, make_state_dict  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -79,8 +79,7 @@ def draw_targets():
     with torch.no_grad():
         mask = overlap_mask(scene)
         out = model.forward_pairs(scene, iou_mask=mask)
-        conf_obj = torch.cat(confs)
-        cc = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+        cc = pair_cat_confidence(scene, confs, "one category confidence per predicted object")
         score = (out.cand_conf.float() + cc.reshape(-1, 1)) + torch.nn.functional.logsigmoid(out.connectivity.float().reshape(-1, 1))
         score = torch.where(mask.reshape(-1, 1) != 0, score, torch.full_like(score, -float("inf"))).cpu().numpy()
     pred, pidx, S = out.cand_pred.cpu().numpy(), scene.pidx, score.shape[1]
@@ -108,7 +107,7 @@ ev = Evaluator(args, cfg.num_relations, 0.5, TOP_K)
 
 def forward():
     c, _, b, scene = _sgdet_scene(model, feat, depth, cats, boxes, sub2super)
-    return _sgdet_forward(model, c, b, scene, overlap_mask(scene), None, None)
+    return _scoring_forward(model, c, b, scene, overlap_mask(scene), None, None)
 
 
 def meter_route():

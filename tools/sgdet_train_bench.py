@@ -33,8 +33,8 @@ sys.path.insert(0, REPO)
 from scene_graph_commonsense_amd.evaluator import _equiv_matrix                        # noqa: E402
 from scene_graph_commonsense_amd.model import BayesianRelationClassifier               # noqa: E402
 from scene_graph_commonsense_amd.optim import FusedSGD                                 # noqa: E402
-from scene_graph_commonsense_amd.pair_loop import (_sgdet_scene, assign_sgdet_targets, overlap_mask, train_minibatch,  # noqa: E402
-                                                   train_sgdet_minibatch, upload_sgdet_targets)
+from scene_graph_commonsense_amd.pair_loop import (_sgdet_scene, assign_sgdet_targets, overlap_mask, pair_cat_confidence,  # noqa: E402
+                                                   train_minibatch, train_sgdet_minibatch, upload_sgdet_targets)
 from scene_graph_commonsense_amd.pairs import normalise_boxes, sg_target_ptr, sg_target_table       # noqa: E402
 from scene_graph_commonsense_amd.synthetic import HeadConfig, default_sub2super, make_scene_batch, make_state_dict  # noqa: E402
 
@@ -78,8 +78,7 @@ def draw_targets():
     with torch.no_grad():
         mask = overlap_mask(scene)
         out = model.forward_pairs(scene, iou_mask=mask)
-        conf_obj = torch.cat(confs)
-        cc = conf_obj[scene.sub_idx.long()] + conf_obj[scene.obj_idx.long()]
+        cc = pair_cat_confidence(scene, confs, "one category confidence per predicted object")
         score = (out.cand_conf.float() + cc.reshape(-1, 1)) + torch.nn.functional.logsigmoid(out.connectivity.float().reshape(-1, 1))
         score = torch.where(mask.reshape(-1, 1) != 0, score, torch.full_like(score, -float("inf"))).cpu().numpy()
     pred, pidx, S = out.cand_pred.cpu().numpy(), scene.pidx, score.shape[1]
