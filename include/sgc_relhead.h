@@ -776,6 +776,22 @@ int sgc_nms_per_class(const int* cand_cat, const float* cand_conf, const float* 
 int sgc_match_boxes_top2(const float* pred_box, const int* pred_ptr, const float* tgt_box, const int* tgt_ptr, int n_img, int max_tgt,
                          int feature_size, int* top_idx, float* top_iou, void* stream);
 
+/* ----------------------------------------------------------------------------------------------- feature extractor: attention
+ * Multi-head attention forward for head dim 32 (csrc/kernels_attn.hip): what nn.MultiheadAttention computes between its input and
+ * output projections in the 18 attention blocks of DETR-101 (detr.py TransformerEncoderLayer / TransformerDecoderLayer), flash-style:
+ *   out[l,b,h,:] = sum_j softmax_j(scale * q[l,b,h,:] . k[j,b,h,:])[j] * v[j,b,h,:]   over the keys j the mask does not exclude.
+ * Element (l, b, h, d) of a tensor sits at l*sL + b*sB + h*32 + d (torch's [L, B, E] layout, E = 32 H; strides in ELEMENTS, separate
+ * per tensor so that q and k may be column slices of one packed [L, B, 2E] projection).  dtype: 0 = f32, 1 = f16, 2 = bf16, for q, k, v
+ * and out alike; the 16-bit types run both products on v_mfma_f32_16x16x32 with f32 softmax / accumulation (P rounded to the input type
+ * only as the PV operand), f32 on the exact v_mfma_f32_16x16x4_f32.  key_padding_mask [B][Lk] bytes, nonzero = key excluded, NULL = none.
+ * A query whose keys are ALL excluded gets zeros (torch's softmax gives NaN there); Lk == 0 writes zeros; Lq == 0 or B == 0 returns 0
+ * without a launch.  Deterministic (no atomics, fixed summation order).  Bad argument: H < 1, a negative length, unknown dtype,
+ * non-finite scale, a base pointer not 16-byte aligned, a stride that is negative or not a multiple of 8 elements (16-bit) / 4 (f32),
+ * a tensor extent beyond 2^31 elements. */
+int sgc_mha_fwd(const void* q, const void* k, const void* v, const unsigned char* key_padding_mask, void* out,
+                int Lq, int Lk, int B, int H, long q_sL, long q_sB, long k_sL, long k_sB, long v_sL, long v_sB,
+                long o_sL, long o_sB, int dtype, float scale, void* stream);
+
 /* ----------------------------------------------------------------------------------------------- generic-size trunk
  * model.py:110-111 constructs BayesianRelationClassifier(args, input_dim, feature_size, ...) with ANY sizes; the tiled kernels above are
  * specialised to input_dim = 128, feature_size = 32 (every shipped configuration, main.py:49-85).  These entry points run the trunk

@@ -10,7 +10,9 @@ embedding with normalisation, 6+6 post-norm transformer with learned queries, 3-
 reference: the parameter / buffer names and their count (``datasets/vg_scene_graph_annot/detr101_key_after.txt``, kept as the data
 fixture ``tests/golden/detr101_keys.txt``), i.e. the reference's checkpoints load with ``load_state_dict``; the layer wiring is
 checked against ``torch.nn`` building blocks on the CPU (``tests/test_detr_cpu.py``).  This is plain PyTorch on ROCm (MIOpen /
-hipBLASLt underneath) - the feature extractor is upstream of the hot path and frozen (``train_test.py:80-81``)."""
+hipBLASLt underneath) - the feature extractor is upstream of the hot path and frozen (``train_test.py:80-81``).  Opt-in
+(``DETR.set_fused_attention``, default off): the 18 attention blocks through ``attention.mha_forward``, a flash-style HIP kernel
+for their 8 heads of 32 channels, instead of ``nn.MultiheadAttention``'s materialised ``[B*8, L, L]`` scores."""
 import math
 import os
 from typing import List, Optional
@@ -18,6 +20,8 @@ from typing import List, Optional
 import torch
 import torch.nn.functional as F
 from torch import Tensor, nn
+
+from . import attention
 
 
 class NestedTensor:
@@ -156,7 +160,9 @@ def _with_pos(x: Tensor, pos: Optional[Tensor]) -> Tensor:
 
 
 class TransformerEncoderLayer(nn.Module):
-    """Post-norm layer; the position embedding is added to queries and keys only."""
+    """Post-norm layer; the position embedding is added to queries and keys only.  ``fused_attention = True`` sends the attention
+    through ``attention.mha_forward`` (the head-dim-32 HIP kernel) whenever ``attention.fused_route`` allows it."""
+    fused_attention = False
 
     def __init__(self, d=256, nhead=8, ff=2048, dropout=0.1):
         super().__init__()
@@ -167,7 +173,11 @@ class TransformerEncoderLayer(nn.Module):
 
     def forward(self, src, src_mask=None, src_key_padding_mask=None, pos=None):
         q = k = _with_pos(src, pos)
-        src = self.norm1(src + self.dropout1(self.self_attn(q, k, value=src, attn_mask=src_mask, key_padding_mask=src_key_padding_mask)[0]))
+        if self.fused_attention and attention.fused_route(self.self_attn, src_mask, q, src):
+            att = attention.mha_forward(self.self_attn, q, k, src, src_key_padding_mask)
+        else:
+            att = self.self_attn(q, k, value=src, attn_mask=src_mask, key_padding_mask=src_key_padding_mask)[0]
+        src = self.norm1(src + self.dropout1(att))
         return self.norm2(src + self.dropout2(self.linear2(self.dropout(F.relu(self.linear1(src))))))
 
 
@@ -184,6 +194,8 @@ class TransformerEncoder(nn.Module):
 
 
 class TransformerDecoderLayer(nn.Module):
+    fused_attention = False                              # as TransformerEncoderLayer: self- and cross-attention through the HIP kernel
+
     def __init__(self, d=256, nhead=8, ff=2048, dropout=0.1):
         super().__init__()
         self.self_attn = nn.MultiheadAttention(d, nhead, dropout=dropout)
@@ -194,9 +206,16 @@ class TransformerDecoderLayer(nn.Module):
 
     def forward(self, tgt, memory, memory_key_padding_mask=None, pos=None, query_pos=None):
         q = k = _with_pos(tgt, query_pos)
-        tgt = self.norm1(tgt + self.dropout1(self.self_attn(q, k, value=tgt)[0]))
-        att = self.multihead_attn(query=_with_pos(tgt, query_pos), key=_with_pos(memory, pos), value=memory,
-                                  key_padding_mask=memory_key_padding_mask)[0]
+        if self.fused_attention and attention.fused_route(self.self_attn, None, q, tgt):
+            att = attention.mha_forward(self.self_attn, q, k, tgt)
+        else:
+            att = self.self_attn(q, k, value=tgt)[0]
+        tgt = self.norm1(tgt + self.dropout1(att))
+        cq, ck = _with_pos(tgt, query_pos), _with_pos(memory, pos)
+        if self.fused_attention and attention.fused_route(self.multihead_attn, None, cq, ck, memory):
+            att = attention.mha_forward(self.multihead_attn, cq, ck, memory, memory_key_padding_mask)
+        else:
+            att = self.multihead_attn(query=cq, key=ck, value=memory, key_padding_mask=memory_key_padding_mask)[0]
         tgt = self.norm2(tgt + self.dropout2(att))
         return self.norm3(tgt + self.dropout3(self.linear2(self.dropout(F.relu(self.linear1(tgt))))))
 
@@ -268,18 +287,42 @@ class DETR(nn.Module):
         hs = self.transformer(self.input_proj(src), mask, self.query_embed.weight, pos[-1])[0]
         return {"pred_logits": self.class_embed(hs)[-1], "pred_boxes": self.bbox_embed(hs).sigmoid()[-1]}
 
+    def set_fused_attention(self, flag: bool = True) -> "DETR":
+        """Route every attention block (6 encoder self-, 6 decoder self-, 6 decoder cross-attention) through the fused HIP kernel
+        (``attention.mha_forward``) where ``attention.fused_route`` allows it.  A plain attribute: no parameter or buffer moves."""
+        for layer in list(self.transformer.encoder.layers) + list(self.transformer.decoder.layers):
+            layer.fused_attention = bool(flag)
+        return self
+
     @torch.no_grad()
-    def encode(self, images: Tensor, feature_size: Optional[int] = None, autocast: Optional[torch.dtype] = None) -> Tensor:
+    def encode(self, images: Tensor, feature_size: Optional[int] = None, autocast: Optional[torch.dtype] = None,
+               fused_attention: Optional[bool] = None) -> Tensor:
         """``process_image_features`` in one call: stacked images ``[B,3,H,W]`` -> encoder memory ``[B,256,H/32,W/32]``.
         ``autocast=torch.bfloat16`` runs the convolutions / GEMMs on the matrix cores in bf16 (the relation head reads the features
-        as f16 anyway); the default keeps the reference's f32."""
-        dev = images.device
+        as f16 anyway); the default keeps the reference's f32.  ``fused_attention`` overrides the layers' flag for this call.
+        A list of images of unequal size is zero-padded and masked; a non-square map comes back as ``[B,256,h,w]``."""
+        layers = list(self.transformer.encoder.layers)
+        saved = [l.fused_attention for l in layers]
+        try:
+            if fused_attention is not None:
+                for l in layers:
+                    l.fused_attention = bool(fused_attention)
+            return self._encode(images, feature_size, autocast)
+        finally:
+            for l, f in zip(layers, saved):
+                l.fused_attention = f
+
+    def _encode(self, images, feature_size, autocast):
+        images = list(images)                                  # stacked, or a list of images of unequal size (zero-padded, masked)
+        dev = images[0].device
         with torch.autocast(dev.type, dtype=autocast, enabled=autocast is not None):
-            maps, pos = self.backbone(nested_tensor_from_tensor_list(list(images)))
+            maps, pos = self.backbone(nested_tensor_from_tensor_list(images))
             src, mask = maps[-1].decompose()
             tok = self.input_proj(src).flatten(2).permute(2, 0, 1)
             mem = self.transformer.encoder(tok, src_key_padding_mask=mask.flatten(1), pos=pos[-1].flatten(2).permute(2, 0, 1))
         out = mem.permute(1, 2, 0).float()
+        if feature_size is None and src.shape[-2] != src.shape[-1]:
+            return out.reshape(-1, out.shape[1], src.shape[-2], src.shape[-1])
         fs = feature_size or int(round(math.sqrt(out.shape[-1])))
         return out.reshape(-1, out.shape[1], fs, fs)
 
@@ -302,4 +345,6 @@ def build_detr101(args) -> DETR:
             for idx, k in enumerate(present):
                 state[after[idx]] = state.pop(k)
         model.load_state_dict(state, strict=False)           # every parameter except "criterion.empty_weight" (utils.py:115)
+    if args["models"].get("feature_encoder_attention") == "fused":      # opt-in: the attention blocks on the HIP kernel (attention.py)
+        model.set_fused_attention(True)
     return model
